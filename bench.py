@@ -15,10 +15,26 @@ region; the host-side draws of the reference (negative query index, MLM word cho
 every step (drawn for step i + 1 while step i runs on the device).  For N > 1 rank r takes the video groups r::N of a global batch of 32 N groups
 (mesm_amd.ddp.shard_groups): weak scaling, 32 pairs per GPU.
 
+A plain run sets up, runs the W warm-up steps, times the K steps, writes the outputs of the last timed step when
+--dump-outputs DIR is given, and prints the result line: `value` (pairs/s), `ms_per_step`, `dtype` and the step-level
+roofline fractions.  Everything else below -- the settled re-timing, host work per step, the dominant kernel family,
+`families`, the other arithmetics and workloads, the eager / unchanged-caller / PCIe / loader-like steps, the optimizer
+tail, the run-to-run spread and cpu_baseline -- runs only with --full (its fields are null in a plain line).
+
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full
+    python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs DIR
+
+--dump-outputs DIR: what a caller of the timed step receives after its last replay -- the total loss (`loss.npy`), every
+entry of the loss dict (`loss.<name>.npy`) and the gradient (`grad.npy`: every parameter's, concatenated in
+named_parameters() order; see dump_outputs), float32, at most 64 MB in all (beyond that each array is the same seeded
+sample of its elements in every run).  The inputs are seeded (weights,
+batch, host draws, dropout seeds): two runs with the same arguments compute on identical inputs, so two builds can be
+compared output for output.
+
 Prints ONE JSON line on rank 0 (contract in the task statement) including
   roofline     — SURVEY 8d's step-level figures: `step_hbm_frac` = algorithmic bytes of the step
                  (0.272 GB + N_pairs x 109.0 MB) / t_step / 8 TB/s and `step_mfma_frac` = N_pairs x 6.22
-                 GFLOP / t_step / 157.3 TF; and, as achieved / peak / frac, the dominant kernel family
+                 GFLOP / t_step / 157.3 TF; and (--full), as achieved / peak / frac, the dominant kernel family
                  (mesm_gemm_f32: f32 GEMMs whose large products run as three fp16 MFMA products over operands split
                  into two fp16 terms under a wave-owned power-of-two scale, f32 accumulate -- MESM_GEMM_BF16X=6 for
                  round 4's six bf16 products, 0 for f32 MFMA throughout): algorithmic FLOPs per launch / mean launch
@@ -38,7 +54,7 @@ Prints ONE JSON line on rank 0 (contract in the task statement) including
                  `other_workloads_not_in_metric` (C2 / C3b / C5 step times with their roofline fractions), the optimizer tail, the
                  PCIe-inclusive rate, and `loader_like_epoch_not_in_metric`: a stream of loader-shaped batches
                  from host memory through StepCache (pair axis padded, real count on the device);
-  cpu_baseline — the CPU oracle (a port of the reference step, oracle/mesm_oracle.py) timed on
+  cpu_baseline — (--full) the CPU oracle (a port of the reference step, oracle/mesm_oracle.py) timed on
                  this box's host cores on the same workload, train mode (rank 0, N = 1 only): 2 warm-up
                  steps, median of 5.
 """
@@ -89,16 +105,49 @@ def step_work(workload, n_pairs):
     return 0.272e9 + n_pairs * 109.0e6, n_pairs * 6.22e9
 
 
+DUMP_BYTES = 64 * 10 ** 6  # --dump-outputs: all files together (the C3a gradient alone is 55 MB)
+
+
+def dump_outputs(path, total, losses, model):
+    """--dump-outputs: what the last step hands its caller, as float32 .npy files: the total loss (loss.npy), every entry
+    of the loss dict (loss.<name>.npy) and the gradient (grad.npy): every parameter's .grad flattened and concatenated
+    in model.named_parameters() order, zeros for a parameter without one.  The gradient is ONE array because it is one
+    vector to its caller (param.grad are views of one flat buffer; clip_grad_norm_, the optimizer and the all-reduce act
+    on all of it), and because some of its parameters have an exactly zero gradient -- the key-projection biases: softmax
+    does not see a shift shared by every key -- where the kernels' float atomics leave summation noise that differs from
+    run to run and is rounding only at the scale of the whole gradient.  If the files would not fit in DUMP_BYTES, every
+    array is cut down to the same fraction of its elements, picked by a fixed seed (the same elements in every run)."""
+    import numpy as np
+    import torch
+    arrays = {"loss": total}
+    arrays.update(("loss." + k, v) for k, v in losses.items())
+    arrays["grad"] = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1)
+                                for _, p in model.named_parameters()])
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    keep = min(1.0, (DUMP_BYTES - 256 * len(arrays)) / sum(a.nbytes for a in arrays.values()))  # (256: .npy header)
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        if keep < 1.0 and a.size > 1:
+            idx = np.random.RandomState(0).choice(a.size, max(1, int(a.size * keep)), replace=False)
+            a = a.reshape(-1)[np.sort(idx)]
+        np.save(os.path.join(path, k + ".npy"), a)
+    log("outputs of the last timed step: %d arrays in %s" % (len(arrays), path))
+
+
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--workload", default="C3a")
-    ap.add_argument("--cpu-steps", type=int, default=5, help="timed oracle steps for cpu_baseline (0 = skip)")
+    ap.add_argument("--cpu-steps", type=int, default=5, help="timed oracle steps for cpu_baseline (0 = skip; --full only)")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="skip the informational sections (profiling runs)")
     ap.add_argument("--eager", action="store_true", help="launch every kernel from Python (no HIP graph)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run every informational measurement and check (see the module docstring)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the loss entries and gradients of the last timed step to DIR/<name>.npy")
     return ap.parse_args()
 
 
@@ -331,11 +380,14 @@ def main():
     import numpy as _np
     _np.random.seed(99 + rank)    # (the vectorized draws read numpy's global stream, mesm_amd/draws.py)
 
+    eager_losses = {}
+
     def eager_step():
         out = model(**batch, dataset_name=args.dataset_name, is_training=True)
         losses, total = crit(out, batch, True)
         model.zero_grad(set_to_none=True)
         total.backward()  # the reducer's finish() runs as an engine callback for world > 1
+        eager_losses.update(losses)
         return total
 
     ddp_mode = None
@@ -497,6 +549,11 @@ def main():
     t_step = dt / opt.steps
     log("timed region: %.3f ms/step" % (t_step * 1e3))
 
+    def dump():  # before anything else runs the step again
+        if opt.dump_outputs and rank == 0:
+            dump_outputs(opt.dump_outputs, last, eager_losses if opt.eager else gstep.losses, model)
+    dump()
+
     # the step-level roofline figures exist as soon as the headline does: a watchdog line (diagnostics that stall) carries them
     _sb, _sf = step_work(opt.workload, n_pairs)
     _WATCHDOG["roofline"] = {"bound": "mfma", "achieved": None, "peak": PEAK_F32_MFMA_TFLOPS, "unit": "TFLOP/s", "frac": None,
@@ -534,6 +591,7 @@ def main():
             ddp_diag[best + "_ms_per_step"] = dt2 / opt.steps * 1e3
             if dt2 / opt.steps < t_step:
                 t_step = dt2 / opt.steps
+                dump()
                 ddp_mode = ("own RCCL communicator (mesm_ddp_*, %d ranks by ncclCommCount), 1/N folded into the loss gradient, "
                             "form %s recorded in the step graph; verified against and faster than `after` (config.ddp_diag)"
                             % (ddp_diag.get("rccl_ranks", -1), best))
@@ -549,7 +607,7 @@ def main():
     # percent slow), and the HIP-event MEDIAN per step of BASELINE.md section 4 (one event pair per step on the step's
     # stream, outside the timed region so that no event record sits inside it).
     settled = None
-    if not opt.eager:
+    if opt.full and not opt.eager:
         for _ in range(SETTLE_STEPS):
             step()
         fence()
@@ -581,7 +639,7 @@ def main():
     # waits for an earlier replay (in the timed loop the arena upload's back-pressure -- at most two steps ahead of
     # the device -- makes step() LAST as long as the device step; that wait is not host work)
     host_ms = None
-    if not opt.eager:
+    if opt.full and not opt.eager:
         hs = 0.0
         for _ in range(opt.steps):
             torch.cuda.synchronize()
@@ -592,7 +650,7 @@ def main():
         host_ms = hs / opt.steps * 1e3
         log("host work per step %.3f ms" % host_ms)
 
-    extras = rank == 0 and not opt.no_extras
+    extras = opt.full and rank == 0 and not opt.no_extras
     # the fallback path of ragged / unseen batch shapes before their graph exists: every launch from Python
     eager_ms = None
     if extras and not opt.eager and world == 1:
@@ -754,7 +812,7 @@ def main():
     roofline["step_hbm_frac"] = sbytes / t_step / (PEAK_HBM_TBS * 1e12)
     roofline["step_mfma_frac"] = sflops / t_step / (PEAK_F32_MFMA_TFLOPS * 1e12)
     roofline["step_bytes"], roofline["step_flops"] = sbytes, sflops
-    if not opt.no_roofline and rank == 0 and world == 1:
+    if opt.full and not opt.no_roofline and rank == 0 and world == 1:
         # the GEMM launches of one captured step, replayed back to back from C++ with a HIP-event
         # pair around every launch (same arguments and buffers as the graph; see mesm_gemm_tape)
         istep = GraphedStep(model, crit, batch, args.dataset_name, warmup=1, instrument=True)
@@ -1001,7 +1059,7 @@ def main():
         def child(**env):
             try:
                 r = subprocess.run([sys.executable, os.path.abspath(__file__), "--steps", str(opt.steps), "--warmup",
-                                    str(opt.warmup), "--cpu-steps", "0", "--no-extras"],
+                                    str(opt.warmup), "--cpu-steps", "0", "--no-extras", "--full"],
                                    env=dict(os.environ, **env), capture_output=True, text=True, timeout=300)
                 lj = json.loads(r.stdout.strip().splitlines()[-1])
                 return {"ms_per_step": lj["ms_per_step"], "gemm_tflops": lj["roofline"]["achieved"],
@@ -1079,7 +1137,7 @@ def main():
                 others[w] = {"error": "%s: %s" % (type(e).__name__, e)}
 
     cpu_baseline = None
-    if rank == 0 and world == 1 and opt.cpu_steps > 0:
+    if opt.full and rank == 0 and world == 1 and opt.cpu_steps > 0:
         from oracle import mesm_oracle as O
         sd = {k: v.detach().cpu() for k, v in model.state_dict().items()}
         cfg = dict(vars(args))
@@ -1119,7 +1177,7 @@ def main():
                                       wl["v_feat_dim"], wl["t_feat_dim"], wl["vocab_size"] + 1),
                        "global_pairs": n_pairs * world, "parallelism": "dp%d" % world,
                        "launch": "eager" if opt.eager else "hip-graph", "ddp": ddp_mode, "ddp_diag": ddp_diag,
-                       "host_draws": draws_mode(),
+                       "host_draws": draws_mode(), "full": opt.full,
                        "settled_not_in_metric": settled,
                        "eager_ms_per_step_not_in_metric": eager_ms,
                        # train.py:64-72 verbatim with the optimizer train.py itself gets from build_optimizer (line 115; all three

@@ -1,8 +1,9 @@
 """The production (vectorized) host draws have the reference's distribution.
 
-Both forms of mesm_amd.draws -- the loop-for-loop reference stream and the vectorized one -- and, where
-/root/reference is present (the build container), the reference's own `sample_outclass_neg` / `MESM._mask_words`,
-are held to the EXACT probabilities with a chi-square test on 20k draws:
+Both forms of mesm_amd.draws -- the loop-for-loop reference stream and the vectorized one -- and the draws of the
+reference's own `sample_outclass_neg` / `MESM._mask_words` (recorded under this file's seeds in
+tests/golden/draw_laws.npz by tools/gen_golden_draw_laws.py) are held to the EXACT probabilities with a chi-square test
+on 20k draws (5k for the loop forms):
 
   * negatives (utils/data_utils.py:113-124): uniform over the pairs of the other video groups;
   * masked words (model/model.py:361-384): k = max(l // 3, 1) of the first l positions by successive sampling without
@@ -11,7 +12,6 @@ are held to the EXACT probabilities with a chi-square test on 20k draws:
 """
 import itertools
 import os
-import sys
 
 import numpy as np
 import pytest
@@ -67,35 +67,26 @@ def _chi2_ok(counts, expect):
     return stat <= chi2.ppf(1 - ALPHA, int(live.sum()) - 1), stat
 
 
-def _ref_functions():
-    root = "/root/reference"
-    if not os.path.isdir(root):
-        return None
-    sys.path.insert(0, root)
-    try:
-        from model.model import MESM as RefMESM
-        from utils.data_utils import sample_outclass_neg
-        return RefMESM, sample_outclass_neg
-    except Exception:  # the reference's imports need packages this box may lack
-        return None
-    finally:
-        sys.path.remove(root)
+def _reference_draws():
+    """the reference's own draws, one array per call in the order they were drawn: `neg` [n, N] and, per `weighted`,
+    the masked-word matrices [n, len(LENS), LW]"""
+    z = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "draw_laws.npz"))
+    n, rows, cols = z["mask_shape"].tolist()
+    masks = {wt: np.unpackbits(z[key], axis=1, count=rows * cols).reshape(n, rows, cols).astype(bool)
+             for wt, key in ((True, "mask_w"), (False, "mask_u"))}
+    return z["neg"].astype(np.int64), masks
 
 
 def _neg_samplers():
-    s = {"vectorized": lambda: draws.neg_index_vectorized(GROUPS),
-         "reference-stream": lambda: draws.neg_index_reference(GROUPS).numpy()}
-    ref = _ref_functions()
-    if ref is not None:
-        s["reference"] = lambda: ref[1](torch.tensor(GROUPS)).numpy()
-    return s
+    ref = iter(_reference_draws()[0])
+    return {"vectorized": lambda: draws.neg_index_vectorized(GROUPS),
+            "reference-stream": lambda: draws.neg_index_reference(GROUPS).numpy(),
+            "reference": lambda: next(ref)}
 
 
 @pytest.mark.parametrize("which", ["vectorized", "reference-stream", "reference"])
 def test_negative_draw_is_uniform_over_the_other_groups(which):
     samplers = _neg_samplers()
-    if which not in samplers:
-        pytest.skip("/root/reference is not importable here")
     np.random.seed(11)
     torch.manual_seed(11)
     N = sum(GROUPS)
@@ -113,22 +104,16 @@ def test_negative_draw_is_uniform_over_the_other_groups(which):
 
 def _mask_samplers():
     wm, w = _mask(), _weights()
-    s = {"vectorized": lambda wt: draws.masked_words_vectorized(wm, w if wt else None),
-         "reference-stream": lambda wt: draws.masked_words_reference(wm, w if wt else None).bool().numpy()}
-    ref = _ref_functions()
-    if ref is not None:
-        feat, tok = torch.zeros(len(LENS), LW, 1), torch.zeros(1)
-        s["reference"] = lambda wt: ref[0]._mask_words(None, feat, wm, tok, proj=False,
-                                                       weight=w if wt else None)[1].bool().numpy()
-    return s
+    ref = {wt: iter(m) for wt, m in _reference_draws()[1].items()}
+    return {"vectorized": lambda wt: draws.masked_words_vectorized(wm, w if wt else None),
+            "reference-stream": lambda wt: draws.masked_words_reference(wm, w if wt else None).bool().numpy(),
+            "reference": lambda wt: next(ref[wt])}
 
 
 @pytest.mark.parametrize("weighted", [True, False])
 @pytest.mark.parametrize("which", ["vectorized", "reference-stream", "reference"])
 def test_masked_word_draw_has_the_successive_sampling_law(which, weighted):
     samplers = _mask_samplers()
-    if which not in samplers:
-        pytest.skip("/root/reference is not importable here")
     np.random.seed(13)
     n = DRAWS if which == "vectorized" else DRAWS // 4
     w = torch.nn.functional.normalize(_weights().float(), dim=1, p=1).numpy().astype(np.float64)
