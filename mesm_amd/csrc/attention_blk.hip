@@ -890,8 +890,11 @@ __global__ __launch_bounds__(BT) void attn_blk_fwd_long_kernel(const MesmAttnArg
         } else {
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
-            float pd = (m_run == -INFINITY) ? 0.0f : __expf(sv[r] - m_run) * inv_l;
-            if (DROP) pd = mesm_hash32(rowi + (uint32_t)(jc + jr + r), drop_seed) >= thresh ? pd * inv_keep : 0.0f;
+            // (a fully masked row: exp(-inf + inf) = NaN, dropped or not, like the reference's softmax over -inf)
+            float pd = __expf(sv[r] - m_run) * inv_l;
+            if (DROP)
+              pd = (m_run == -INFINITY || mesm_hash32(rowi + (uint32_t)(jc + jr + r), drop_seed) >= thresh) ? pd * inv_keep
+                                                                                                             : 0.0f;
             const float* vrow = Vs + (jr + r) * BS + jl;
             oa[0] = mfma16(pd, vrow[0], oa[0]);
             oa[1] = mfma16(pd, vrow[16], oa[1]);
@@ -906,7 +909,7 @@ __global__ __launch_bounds__(BT) void attn_blk_fwd_long_kernel(const MesmAttnArg
       const float L = add_xor32(add_xor16(part_l));
       m_run = M;
       l_run = L;
-      inv_l = 1.0f / L;  // (a fully masked row: 0 * inf = NaN, like the reference's softmax over -inf)
+      inv_l = 1.0f / L;
     }
   }
   if (active) {
