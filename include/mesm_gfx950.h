@@ -396,6 +396,20 @@ int mesm_windows(const float* logits, const float* spans, const float* duration,
                  int32_t Q, void* stream);
 
 /*
+ * Submission rows (eval.py:63-92, utils/post_processing.py:22-47): out (N, Q, 3) float64 [start, end, score] per query,
+ * bit-identical to mesm_amd.postprocess.predict_windows.  The raw rows use mesm_windows' fp32 arithmetic; with sort != 0
+ * each query's Q rows are ranked by score, descending and stable (Python's sorted(..., reverse=True)); every value is
+ * rounded to 4 decimals as float(f"{x:.4f}") does (rint(double(x) * 1e4) / 1e4, correctly rounded division); the window
+ * ends are cast to fp32 and clamped to [min_ts_val, max_ts_val] like np.clip (replaced only when strictly outside: a -0.0
+ * against a bound of 0 stays -0.0); with clip_len != -1 they are snapped to
+ * rintf(w / clip_len) * clip_len in fp32; the score is cast to fp32 and rounded to 4 decimals again.  One wave per
+ * query: Q <= 64 (MESM_EINVAL beyond, and for clip_len == 0).  Non-finite logits / spans are outside the contract:
+ * every row is still written once (a NaN score ranks like -inf), its values are unspecified.
+ */
+int mesm_windows_rows(const float* logits, const float* spans, const float* duration, double* out, int32_t N,
+                      int32_t Q, float clip_len, float min_ts_val, float max_ts_val, int32_t sort, void* stream);
+
+/*
  * Decoder reference-point arithmetic, fused (each was ~8 / ~5 ATen launches, twice that in backward):
  *   ref_update   out = sigmoid(delta + inverse_sigmoid(ref)), inverse_sigmoid as transformer.py:36-40
  *                (clamp to [0,1], eps 1e-3): transformer.py:392-394 (new reference points) and

@@ -166,6 +166,8 @@ PROTOTYPES = {
     "mesm_query_sine_bwd": (ctypes.c_int, [c_ptr, c_ptr, c_ptr, _i64, _i32, c_ptr]),
     "mesm_dropout": (ctypes.c_int, [c_ptr, c_ptr, _i64, _f32, _u32, c_ptr, c_ptr]),
     "mesm_windows": (ctypes.c_int, [c_ptr, c_ptr, c_ptr, c_ptr, _i32, _i32, c_ptr]),
+    "mesm_windows_rows": (ctypes.c_int, [c_ptr, c_ptr, c_ptr, c_ptr, _i32, _i32, ctypes.c_float, ctypes.c_float,
+                                         ctypes.c_float, _i32, c_ptr]),
     "mesm_ref_update_fwd": (ctypes.c_int, [c_ptr, c_ptr, c_ptr, _i64, _f32, c_ptr]),
     "mesm_ref_update_bwd": (ctypes.c_int, [c_ptr] * 5 + [_i64, _f32, c_ptr]),
     "mesm_ref_init_fwd": (ctypes.c_int, [c_ptr, c_ptr, _i32, _i32, c_ptr]),

@@ -25,6 +25,16 @@ belongs to an older forward raises; the outputs carry no autograd history of the
 build's criterion; anything else that wants gradients through them needs the eager path).  `MESM_AUTOGRAPH=0`, or
 `model.autograph(False)`, keeps every step eager.
 
+Evaluation calls (eval.py:63,102: `model(**batch, is_training=False)` under no_grad with the model in eval() mode, then
+`criterion(outputs, batch, is_training=False)`) stay eager unless asked: `model.autograph(eval=True)` or
+MESM_AUTOGRAPH_EVAL=1 replays them from forward-only graphs (graphed.EvalGraphedStep: the forward and, once the criterion
+is known and the batch carries its targets, the criterion in the same graph).  Same rules as training -- eager first
+visit, capture on the second, pad / pairs buckets -- with a cache of their own (their own budget: evaluation never evicts
+a training graph, nor the other way round).  The negative-query draw is made where the eager call makes it, from the
+same global RNG stream.  The outputs are the caller's: one device copy out of graph memory, cut to the real pairs and the
+caller's clip / word extents; `criterion(outputs, batch, is_training=False)` with that batch returns the losses of the
+same replay, with any other batch it runs eagerly on those copies.
+
 Buckets: key = (dataset, train/eval mode, pairs, clip / word extents, feature dims, group-size bucket, batch keys).
 The reference's loaders emit another (pairs, Lv, Lw) almost every batch; `model.autograph(pad=(max_v_l, max_words_l),
 pairs=8)` pads every batch like graphed.StepCache does (clips / words to fixed extents, the pair axis to a multiple of
@@ -47,6 +57,7 @@ class AutoOutputs(dict):
     _auto_gen = -1
     _auto_batch = None
     _mesm_side = None    # the stream an eager forward ran on when that was not the caller's (eager outputs only)
+    _eval_losses = None  # (losses, total) captured with a replayed evaluation forward (replayed eval outputs only)
 
 
 class _Backward(torch.autograd.Function):
@@ -127,6 +138,15 @@ def _enabled_default():
     return os.environ.get("MESM_AUTOGRAPH", "1") != "0"
 
 
+def _eval_default():
+    return os.environ.get("MESM_AUTOGRAPH_EVAL", "0") == "1"
+
+
+# evaluation outputs with a clip axis / a word axis (+ leading sentence slot) at dim 1: cut back to the caller's extents
+_EVAL_CLIP_OUT = ("saliency_scores", "neg_saliency_scores", "projed_video_feat", "enhanced_video_feat")
+_EVAL_WORD_OUT = {"projed_words_feat": 0, "expanded_words_feat": 1, "expanded_words_mask": 1, "words_mask": 0}
+
+
 GROUP_CAPS = (1, 2, 3, 5, 9, 16, 32, 64)  # largest-video-group buckets (9 = the QVHighlights maximum, base.py:116-162)
 
 
@@ -148,11 +168,21 @@ class AutoGraph:
         self.fetch = _Fetch()
         self.spec = None
         self.host_side = 0    # forwards served from the collate's host copies (batch["_host"]) instead of a fetch
+        # evaluation calls (opt-in): their own graphs, budget and counters
+        self.eval_enabled = _eval_default()
+        self.eval_steps = OrderedDict()  # key -> [EvalGraphedStep]
+        self.eval_seen = {}
+        self.eval_bad = set()
+        self.eval_max_graphs = int(os.environ.get("MESM_AUTOGRAPH_EVAL_MAX", "16"))
+        self.eval_captures = self.eval_replays = self.eval_eager = 0
+        self.eval_neg = None  # the draw of an eval call that ends up eager after all (it has been made already)
 
     # ------------------------------------------------------------------ configuration
-    def configure(self, enabled=None, pad=None, pairs=None, max_graphs=None):
+    def configure(self, enabled=None, pad=None, pairs=None, max_graphs=None, eval=None):
         if enabled is not None:
             self.enabled = bool(enabled)
+        if eval is not None:
+            self.eval_enabled = bool(eval)
         if pad is not None:
             self.pad = tuple(pad)
         if pairs is not None:
@@ -167,6 +197,9 @@ class AutoGraph:
             if self.steps:  # graphs captured with another criterion object: its weights / losses are baked in
                 self.steps.clear()
                 self.seen.clear()
+            if self.eval_steps:
+                self.eval_steps.clear()
+                self.eval_seen.clear()
 
     # ------------------------------------------------------------------ forward
     @staticmethod
@@ -242,6 +275,12 @@ class AutoGraph:
                 and kwargs.get("neg_index") is None and kwargs.get("masked_words") is None
                 and not torch.cuda.is_current_stream_capturing())
 
+    def eligible_eval(self, model, batch, kwargs):
+        return (self.enabled and self.eval_enabled and not self.busy and kwargs.get("is_training") is False
+                and not torch.is_grad_enabled() and not model.training and kwargs.get("plan") is None
+                and kwargs.get("neg_index") is None and kwargs.get("masked_words") is None
+                and batch["video_feat"].is_cuda and not torch.cuda.is_current_stream_capturing())
+
     def eager_stream(self, dev):
         """the stream an EAGER grad-enabled forward of a caller on the default stream runs on (None: where the caller is)"""
         if not self.enabled or self.busy or not torch.is_grad_enabled() or torch.cuda.is_current_stream_capturing():
@@ -313,20 +352,159 @@ class AutoGraph:
         res._auto_step, res._auto_gen, res._auto_batch = step, self.gen, batch
         return res
 
+    # ------------------------------------------------------------------ evaluation forward
+    _TARGETS = ("norm_span", "norm_moment", "video_mask")
+
+    def forward_eval(self, batch, dataset_name):
+        """-> AutoOutputs of a replayed evaluation call, or None: run it eagerly (with `eval_neg` when the draw is made)"""
+        from . import draws
+        self.eval_neg = None
+        model = self.model()
+        crit = self.crit() if self.crit is not None else None
+        try:
+            if getattr(self, "_eval_spec_key", None) != (dataset_name, id(crit)):
+                from .hostplan import HostSpec
+                self.eval_spec = HostSpec.from_model(model, crit, dataset_name)
+                self._eval_spec_key = (dataset_name, id(crit))
+            spec = self.eval_spec
+            with_crit = crit is not None and all(k in batch for k in self._TARGETS) \
+                and ("saliency_label" in batch or "clip_mask" in batch)
+            work = self._with_host_side(batch, spec)
+            if work is not None:
+                shaped = host = self._shaped(work)
+            else:
+                shaped = self._shaped({k: v for k, v in batch.items() if k != "_host"})
+                host = None
+            if shaped is None:
+                self.eval_eager += 1
+                return None
+            if host is None:
+                from .graphed import GraphedStep
+                host = self.fetch(shaped, spec, GraphedStep.BIG)
+            seen_key, gcap = self._key(model, shaped, dataset_name, host["num_clips"])
+            # (visits are counted per shape: the first call of an epoch may come before the criterion introduced itself)
+            key = seen_key + (with_crit,)
+        except Exception:
+            self.eval_eager += 1
+            return None
+        if key in self.eval_bad or (key not in self.eval_steps and self.eval_seen.get(seen_key, 0) < 1):
+            self.eval_seen[seen_key] = self.eval_seen.get(seen_key, 0) + 1
+            self.eval_eager += 1
+            return None
+        # the eager call's one host draw, here: same stream, same place in it (the real groups; padding pairs -> 0)
+        groups = [int(g) for g in host["num_clips"].tolist()]
+        n_real = shaped.get("_n_real")
+        neg = draws.neg_index(groups, n_real)
+        n = batch["video_feat"].shape[0]
+        self.eval_neg = neg[:n]
+        step = None
+        for s in self.eval_steps.get(key, []):
+            try:
+                s._draws = (neg, None)
+                s.load_batch(shaped, redraw=False, host=host)
+            except ValueError:
+                continue
+            step = s
+            break
+        if step is None:
+            step = self._capture_eval(key, gcap, shaped, dataset_name, crit if with_crit else None, neg)
+            if step is None:
+                self.eval_eager += 1
+                return None
+        else:
+            self.eval_steps.move_to_end(key)
+        buf = step.replay()
+        out, losses, total = step.unpack(buf)
+        self.eval_neg = None
+        self.eval_replays += 1
+        res = AutoOutputs(self._eval_extents(model, out, batch, n))
+        res._mesm_model = self.model
+        res._auto_batch = batch
+        if losses is not None:
+            res._eval_losses = (losses, total)
+        return res
+
     @staticmethod
-    def _real_rows(out, n):
-        """outputs of a pair-padded replay, cut back to the caller's pairs (views; every entry leads with the pair axis)"""
-        cut = lambda t: t[:n] if torch.is_tensor(t) and t.dim() >= 1 else t
-        return {k: ([{kk: cut(vv) for kk, vv in d.items()} for d in v] if isinstance(v, list) else cut(v))
+    def _extents(model, batch):
+        """(clips, words) of the forward's outputs for `batch` (token ids are cut to max_words_l by the CLIP encoder)"""
+        W = batch["words_id"]
+        Lw = W.shape[1]
+        if W.dim() == 2:
+            from .text_encoder import CLIPTextEncoder
+            if isinstance(model.text_encoder, CLIPTextEncoder):
+                Lw = min(Lw, model.max_words_l)
+        return batch["video_feat"].shape[1], Lw
+
+    def _check_eval_axes(self, model, step, shaped):
+        """a graph of padded clip / word extents (pad=...) serves callers of smaller ones, so it may only hand out outputs
+        whose clip / word axis the cut knows (_EVAL_CLIP_OUT / _EVAL_WORD_OUT): any other output with such an extent at
+        dim 1 -- a new output of the model -- refuses the capture (the shape stays eager) instead of coming back padded"""
+        if self.pad is None:
+            return
+        Lv_p, Lw_p = AutoGraph._extents(model, shaped)
+        padded = {Lv_p} | {Lw_p + c for c in set(_EVAL_WORD_OUT.values())}
+        for path, _, shape, _, _ in step.layout:
+            k = path if isinstance(path, str) else (path[2] if len(path) == 3 else None)
+            if k is None or len(shape) < 2 or k in _EVAL_CLIP_OUT or k in _EVAL_WORD_OUT:
+                continue
+            if shape[1] in padded:
+                raise ValueError("output %r %s has a padded clip / word extent at dim 1 that the eval cut does not know"
+                                 % (k, shape))
+
+    @staticmethod
+    def _eval_extents(model, out, batch, n):
+        """outputs of a padded replay with the eager call's shapes: the real pairs, the caller's clips and words (views)"""
+        Lv, Lw = AutoGraph._extents(model, batch)
+
+        def cut(k, t):
+            if not torch.is_tensor(t) or t.dim() < 1:
+                return t
+            t = t[:n]
+            if t.dim() >= 2:
+                if k in _EVAL_CLIP_OUT:
+                    t = t[:, :Lv]
+                elif k in _EVAL_WORD_OUT:
+                    t = t[:, :Lw + _EVAL_WORD_OUT[k]]
+            return t
+        return {k: ([{kk: cut(kk, vv) for kk, vv in d.items()} for d in v] if isinstance(v, list) else cut(k, v))
                 for k, v in out.items()}
 
-    def _capture(self, key, gcap, batch, dataset_name, crit):
-        from .graphed import SplitGraphedStep
+    def eval_criterion(self, crit, outputs, targets, is_training):
+        """the losses captured with a replayed evaluation forward, or None (the caller runs the eager criterion)"""
+        if is_training or self.crit is None or self.crit() is not crit or outputs._eval_losses is None:
+            return None
+        b = outputs._auto_batch
+        if targets is not b and any(targets.get(k) is not b.get(k) for k in b):
+            return None
+        losses, total = outputs._eval_losses
+        return dict(losses), total
+
+    def _capture_eval(self, key, gcap, batch, dataset_name, crit, neg):
+        from .graphed import EvalGraphedStep
         model = self.model()
-        gb = model.gradbuf()
-        while sum(len(v) for v in self.steps.values()) >= self.max_graphs and self.steps:
-            self.steps.popitem(last=False)
-        dev = batch["video_feat"].device
+        while sum(len(v) for v in self.eval_steps.values()) >= self.eval_max_graphs and self.eval_steps:
+            self.eval_steps.popitem(last=False)
+        self.busy = True
+        try:
+            step = EvalGraphedStep(model, crit, self._static(batch), dataset_name, warmup=1, caps="auto",
+                                   group_cap=gcap if gcap > 1 else None, neg_index=neg)
+            self._check_eval_axes(model, step, batch)
+        except Exception as e:
+            self.eval_bad.add(key)
+            warnings.warn("mesm_amd.autograph: eval capture failed for %r (%s: %s); this shape stays eager"
+                          % (key, type(e).__name__, e))
+            step = None
+        finally:
+            self.busy = False
+        if step is None:
+            return None
+        self.eval_steps.setdefault(key, []).append(step)
+        self.eval_captures += 1
+        return step
+
+    @staticmethod
+    def _static(batch):
+        """the capture's own copy of a (shaped) device batch: big tensors padded to the pair extent on the device"""
         clone = lambda v: v.clone() if torch.is_tensor(v) else v
         static = {}
         for k, v in batch.items():
@@ -343,6 +521,22 @@ class AutoGraph:
                 t = static[kk]
                 if t.shape[0] < P:
                     static[kk] = torch.cat([t, t[:1].expand((P - t.shape[0],) + tuple(t.shape[1:]))]).contiguous()
+        return static
+
+    @staticmethod
+    def _real_rows(out, n):
+        """outputs of a pair-padded replay, cut back to the caller's pairs (views; every entry leads with the pair axis)"""
+        cut = lambda t: t[:n] if torch.is_tensor(t) and t.dim() >= 1 else t
+        return {k: ([{kk: cut(vv) for kk, vv in d.items()} for d in v] if isinstance(v, list) else cut(v))
+                for k, v in out.items()}
+
+    def _capture(self, key, gcap, batch, dataset_name, crit):
+        from .graphed import SplitGraphedStep
+        model = self.model()
+        gb = model.gradbuf()
+        while sum(len(v) for v in self.steps.values()) >= self.max_graphs and self.steps:
+            self.steps.popitem(last=False)
+        static = self._static(batch)
         # the warm-up and capture steps run real backward passes: the caller's gradients are put back afterwards
         had = [p.grad is not None for p in gb.params]
         saved = gb.flat.clone() if (gb.flat is not None and any(had)) else None

@@ -373,6 +373,10 @@ class Criterion(nn.Module):
             auto = getattr(m, "_auto", None)
             if auto is not None and outputs._auto_step is not None:
                 return auto.criterion(self, outputs, targets, is_training)  # replayed forward: replay the criterion graph
+            if auto is not None and outputs._eval_losses is not None:
+                res = auto.eval_criterion(self, outputs, targets, is_training)  # captured with the evaluation forward
+                if res is not None:
+                    return res
             if auto is not None and not auto.busy:
                 auto.note_criterion(self)  # eager step: the model learns which criterion its steps are captured with
             side = outputs._mesm_side

@@ -111,6 +111,8 @@ class _PulledGraph:
 class GraphedStep:
     BIG = 1 << 20  # batch tensors above 1 MiB (video_feat, word features) are copied on their own
     DRAWN = ("p.neg_index", "p.masked_words")  # what redraw() changes: the host RNG draws of a step
+    TRAIN = True     # a training step (EvalGraphedStep: a forward-only evaluation step)
+    _targets = True  # the arena holds the criterion's target plan
 
     def __init__(self, model, criterion, batch, dataset_name, warmup=3, instrument=False, reducer=None,
                  caps=None, group_cap=None):
@@ -154,12 +156,15 @@ class GraphedStep:
                       if dev.type == "cuda" and os.environ.get("MESM_STEP_PULL", "0") == "1" else None)
         v = self.arena.views
         self.plan = model.plan_from({k[2:]: t for k, t in v.items() if k.startswith("p.")}, self._pmeta)
-        self.tplan = TargetPlan.__new__(TargetPlan)
-        self.tplan.adopt({k[2:]: t for k, t in v.items() if k.startswith("t.")}, self._tmeta)
+        self.tplan = None
+        if self._tmeta is not None:
+            self.tplan = TargetPlan.__new__(TargetPlan)
+            self.tplan.adopt({k[2:]: t for k, t in v.items() if k.startswith("t.")}, self._tmeta)
         for k, t in v.items():
             if k.startswith("b."):
                 self.batch[k[2:]] = t
-        self.batch["_target_plan"] = self.tplan
+        if self.tplan is not None:
+            self.batch["_target_plan"] = self.tplan
         if self._n_real is not None:
             self.batch["_n_valid"] = v["p.n_valid"]
         gb = model.gradbuf()
@@ -192,7 +197,8 @@ class GraphedStep:
             dot = os.environ.get("MESM_GRAPH_DOT")
             if dot:
                 self.graph.enable_debug_mode()
-            model.zero_grad(set_to_none=True)
+            if self.TRAIN:
+                model.zero_grad(set_to_none=True)
             if instrument:  # record the GEMM launches of the captured step (bench roofline)
                 kn.gemm_tape(True)
             # capture_error_mode="thread_local": the process group's watchdog THREAD polls the events of earlier
@@ -230,7 +236,7 @@ class GraphedStep:
         """hostplan.HostSpec.host_arrays with this step's groups / capacities: {name: numpy array} of everything small
         the captured step reads, the two metas and the word mask"""
         return self.spec.host_arrays(host, self._groups, self.caps, self._n_real, neg_index, masked_words, self.BIG,
-                                     targets=targets)
+                                     targets=targets and self._targets, is_training=self.TRAIN)
 
     def _param_ptrs(self):
         gb = self.model.gradbuf()
@@ -321,7 +327,8 @@ class GraphedStep:
             self.arena.upload(arr, only=[k for k in arr if not k.startswith("t.")])
         else:
             self.arena.upload(arr)
-            self.tplan.sizes, self.tplan.sumT = tmeta["sizes"], tmeta["sumT"]
+            if tmeta is not None:
+                self.tplan.sizes, self.tplan.sumT = tmeta["sizes"], tmeta["sumT"]
         for k, cur in self.batch.items():
             v = batch.get(k)
             if k.startswith("_"):
@@ -546,6 +553,121 @@ class SplitGraphedStep(GraphedStep):
         if grad is not None:
             self.seed.copy_(grad)
         self.g_bwd.replay()
+
+
+class EvalGraphedStep(GraphedStep):
+    """The evaluation call of the reference (eval.py:63,102), forward only, captured in ONE graph:
+    `model(**batch, is_training=False)` with the model in eval() mode (no dropout, no masked-LM branch, no backward) and,
+    with a criterion, `criterion(outputs, batch, is_training=False)` behind it.  The arena, the index plans (the eval
+    plan: no masked-word arrays), the capacities and the pair padding are GraphedStep's.  The one host draw of the
+    forward -- the negative query index (sample_outclass_neg) -- is the caller's: `load_batch` keeps `_draws`, which the
+    caller sets before every replay (autograph.py draws it exactly where the eager call would).
+
+    Everything the replay wrote -- outputs, the loss vector, the total -- is packed inside the graph into ONE static byte
+    buffer (`pack`), so that a caller takes its own copy of a replay with a single device copy (`replay_copy`)."""
+    TRAIN = False
+    DRAWN = ("p.neg_index",)
+
+    def __init__(self, model, criterion, batch, dataset_name, warmup=1, caps=None, group_cap=None, neg_index=None):
+        """criterion None: the forward alone.  neg_index: the draw of the first replay (None: drawn here)"""
+        if model.training:
+            raise ValueError("EvalGraphedStep: call model.eval() first (the step is captured in the model's mode)")
+        self._targets = criterion is not None
+        self._draws = (None if neg_index is None else neg_index, None)
+        with torch.no_grad():
+            super().__init__(model, criterion, batch, dataset_name, warmup=warmup, caps=caps, group_cap=group_cap)
+
+    def _host_arrays(self, host, neg_index, masked_words, targets=True):
+        if neg_index is None and getattr(self, "arena", None) is None:
+            neg_index = self._draws[0]  # (the capture's own draw, handed in by the caller)
+        return super()._host_arrays(host, neg_index, None, targets)
+
+    def _step_body(self):
+        b = self.batch
+        out = self.model(**b, dataset_name=self.dataset_name, is_training=False, plan=self.plan)
+        losses = total = None
+        if self.crit is not None:
+            losses, total = self.crit(out, b, False)
+        return out, losses, total
+
+    def _capture(self, side):
+        with torch.cuda.graph(self.graph, stream=side, capture_error_mode="thread_local"):
+            self.counter.add_(1)
+            out, losses, total = self._step_body()
+            self._pack_outputs(out, losses, total)
+
+    def _pack_outputs(self, out, losses, total):
+        """(captured) every output tensor, the loss vector and the total, byte-wise into one buffer; `layout` remembers
+        where each one sits: [(path, dtype, shape, byte offset)] with path = key or (key, layer, subkey)"""
+        items = []
+        for k, v in out.items():
+            if isinstance(v, list):
+                for i, d in enumerate(v):
+                    items += [((k, i, kk), vv) for kk, vv in d.items() if torch.is_tensor(vv)]
+            elif torch.is_tensor(v):
+                items.append((k, v))
+        self.loss_index = None
+        if losses is not None:
+            vals = list(losses.values())
+            pack = getattr(vals[0], "_pack", None) if vals else None
+            if pack is not None and all(getattr(v, "_pack", None) is pack for v in vals):
+                items.append((("_loss_vec",), pack.vec))
+                self.loss_index = {k: int(v._i) for k, v in losses.items()}
+            else:
+                for k, v in losses.items():
+                    items.append((("_loss", k), v.reshape(1)))
+            items.append((("_total",), total.reshape(1)))
+        items.sort(key=lambda kv: -kv[1].element_size())  # (largest element first: every piece stays aligned)
+        self.layout, off = [], 0
+        parts = []
+        for path, t in items:
+            t = t.detach().contiguous()
+            nb = t.numel() * t.element_size()
+            self.layout.append((path, t.dtype, tuple(t.shape), off, nb))
+            parts.append(t.view(-1).view(torch.uint8))
+            off += nb
+        self.pack = torch.cat(parts)
+        self.out_keys = list(out.keys())
+        self.total_shape = tuple(total.shape) if total is not None else None
+
+    def replay(self):
+        """replay the captured call on the loaded batch and draws; -> a fresh copy of its pack (caller-owned memory)"""
+        m = self.model
+        gen = m.__dict__.get("_addr_gen", 0)
+        fp = m._flat_params
+        quick = (fp.data_ptr() if fp is not None else 0, m.gradbuf().flat.data_ptr())
+        if gen != getattr(self, "_addr_gen", None) or quick != getattr(self, "_quick_ptrs", None):
+            if self._param_ptrs() != self._ptrs:
+                raise RuntimeError("EvalGraphedStep: a parameter moved after capture")
+            self._addr_gen, self._quick_ptrs = gen, quick
+        self.graph.replay()
+        return self.pack.clone()
+
+    def unpack(self, buf):
+        """views of a pack copy: (outputs in the eager call's key structure, losses {name: tensor} or None, total or None)"""
+        got, losses, total, aux, vec = {}, {}, None, {}, None
+        for path, dt, shape, off, nb in self.layout:
+            t = buf[off:off + nb].view(dt).view(shape)
+            if isinstance(path, str):
+                got[path] = t
+            elif path[0] == "_loss_vec":
+                vec = t
+            elif path[0] == "_loss":
+                losses[path[1]] = t.reshape(())
+            elif path[0] == "_total":
+                total = t.view(self.total_shape)
+            else:
+                aux.setdefault(path[0], {}).setdefault(path[1], {})[path[2]] = t
+        for k, layers in aux.items():
+            got[k] = [layers[i] for i in sorted(layers)]
+        out = {k: got[k] for k in self.out_keys if k in got}
+        if vec is not None:
+            from .criterion import loss_entries
+            losses = loss_entries(vec, self.loss_index)
+        return out, (losses if self.crit is not None else None), total
+
+    def run(self, redraw=True):
+        raise RuntimeError("EvalGraphedStep is replayed with replay() / unpack()")
 
 
 class StepCache:

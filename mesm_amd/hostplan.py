@@ -26,9 +26,12 @@ class HostSpec:
 
     @classmethod
     def from_model(cls, model, criterion, dataset_name):
+        """criterion None (a forward-only evaluation step without losses): the target fields take the defaults of
+        build_criterion for the dataset; nothing reads them without a criterion"""
+        multi = bool(criterion.multi_clip) if criterion is not None else dataset_name in ["qvhighlights"]
         return cls(rec_fw=bool(model.rec_fw), rec_ss=bool(model.rec_ss), max_words_l=int(model.max_words_l),
                    normalize_txt=bool(model.normalize_txt), num_queries=int(model.num_queries), dataset_name=dataset_name,
-                   multi_clip=bool(criterion.multi_clip), gamma=float(criterion.gamma))
+                   multi_clip=multi, gamma=float(criterion.gamma) if criterion is not None else 0.9)
 
     @classmethod
     def from_args(cls, args):
@@ -99,15 +102,16 @@ class HostSpec:
         tarr, tmeta = TargetPlan.arrays(host, self.multi_clip, self.gamma, T_cap=caps.get("T"), Tmax_cap=caps.get("Tmax"))
         return {"t." + k: v for k, v in tarr.items()}, tmeta
 
-    def host_arrays(self, host, groups, caps, n_real, neg_index, masked_words, big, targets=True):
+    def host_arrays(self, host, groups, caps, n_real, neg_index, masked_words, big, targets=True, is_training=True):
         """{name: numpy array}: "p." the forward's plan, "t." the criterion's target plan, "b." batch tensors of at
         most `big` bytes; plus the two metas and the word mask.  neg_index / masked_words None: drawn here (the caller
-        is the training process); workers pass placeholders and the training process draws (GraphedStep.redraw)."""
+        is the training process); workers pass placeholders and the training process draws (GraphedStep.redraw).
+        is_training=False: the plan of an evaluation forward (no masked-LM arrays, no masked-word draw)."""
         wm = self.words_mask(host)
         P = host["video_mask"].shape[0]
         if wm.shape[0] < P:  # a big feature tensor that arrived with its real rows only (batching.pad_pairs)
             wm = torch.cat([wm, wm[:1].expand(P - wm.shape[0], wm.shape[1])])
-        parr, pmeta = self.plan_arrays(host["video_mask"].numpy(), wm.numpy(), groups, self.dataset_name, True,
+        parr, pmeta = self.plan_arrays(host["video_mask"].numpy(), wm.numpy(), groups, self.dataset_name, is_training,
                                        clip_mask=host["clip_mask"].numpy() if "clip_mask" in host else None,
                                        neg_index=neg_index, masked_words=masked_words,
                                        words_weight=host.get("words_weight"), Lc_cap=caps.get("Lc"),

@@ -400,13 +400,14 @@ class MESM(nn.Module):
         return pl
 
     # ------------------------------------------------------------------ forward
-    def autograph(self, enabled=None, pad=None, pairs=None, max_graphs=None):
+    def autograph(self, enabled=None, pad=None, pairs=None, max_graphs=None, eval=None):
         """Graph replay behind the unchanged `model(...) / criterion(...) / loss.backward()` sequence (autograph.py):
         on by default (MESM_AUTOGRAPH=0 turns it off); `pad=(max_v_l, max_words_l), pairs=8` pads batches like
-        graphed.StepCache so that a loader's ever-changing shapes replay from a handful of graphs."""
+        graphed.StepCache so that a loader's ever-changing shapes replay from a handful of graphs.  eval=True (or
+        MESM_AUTOGRAPH_EVAL=1): evaluation calls (is_training=False, no_grad, model.eval()) replay too."""
         if self._auto is None:
             self._auto = AutoGraph(self)
-        return self._auto.configure(enabled, pad, pairs, max_graphs)
+        return self._auto.configure(enabled, pad, pairs, max_graphs, eval)
 
     def forward(self, video_feat, video_mask, words_id, words_mask, words_weight, num_clips, **kwargs):
         dev = video_feat.device
@@ -419,6 +420,16 @@ class MESM(nn.Module):
             res = auto.forward(batch, kwargs["dataset_name"])
             if res is not None:
                 return res
+        elif auto.eligible_eval(self, {"video_feat": video_feat}, kwargs):
+            batch = dict(video_feat=video_feat, video_mask=video_mask, words_id=words_id, words_mask=words_mask,
+                         words_weight=words_weight, num_clips=num_clips)
+            batch.update({k: v for k, v in kwargs.items() if k not in ("dataset_name", "is_training", "plan")})
+            res = auto.forward_eval(batch, kwargs["dataset_name"])
+            if res is not None:
+                return res
+            if auto.eval_neg is not None:  # the call's draw has been made: the eager forward takes it
+                kwargs = dict(kwargs, neg_index=torch.from_numpy(auto.eval_neg))
+                auto.eval_neg = None
         elif torch.is_grad_enabled() and not auto.busy:
             auto.gen += 1
         side = auto.eager_stream(dev)
