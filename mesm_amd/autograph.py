@@ -43,11 +43,11 @@ pairs=8)` pads every batch like graphed.StepCache does (clips / words to fixed e
 import os
 import warnings
 import weakref
-from collections import OrderedDict
 
 import torch
 
 from . import kernels as kn
+from .batching import group_bucket, shape_batch
 
 
 class AutoOutputs(dict):
@@ -152,30 +152,31 @@ GROUP_CAPS = (1, 2, 3, 5, 9, 16, 32, 64)  # largest-video-group buckets (9 = the
 
 class AutoGraph:
     def __init__(self, model):
+        from .graphed import GraphCache
         self.model = weakref.ref(model)
         self.enabled = _enabled_default()
         self.crit = None
-        self.steps = OrderedDict()  # key -> [SplitGraphedStep]
-        self.seen = {}
-        self.bad = set()
-        self.max_graphs = int(os.environ.get("MESM_AUTOGRAPH_MAX", "16"))
+        self.train_graphs = GraphCache(int(os.environ.get("MESM_AUTOGRAPH_MAX", "16")))  # SplitGraphedStep
         self.pad = None
         self.pairs = None
         self.gen = 0          # forwards of this model (eager ones included): one may be in flight
         self.busy = False     # inside a capture: the model's forward is being called by the step itself
         self.token = None
-        self.captures = self.replays = self.eager = 0
+        self.eager = 0        # first visits of a training bucket (run eagerly)
         self.fetch = _Fetch()
-        self.spec = None
+        self.spec, self._spec_key = None, None  # hostplan.HostSpec of (dataset, criterion object)
         self.host_side = 0    # forwards served from the collate's host copies (batch["_host"]) instead of a fetch
         # evaluation calls (opt-in): their own graphs, budget and counters
         self.eval_enabled = _eval_default()
-        self.eval_steps = OrderedDict()  # key -> [EvalGraphedStep]
-        self.eval_seen = {}
-        self.eval_bad = set()
-        self.eval_max_graphs = int(os.environ.get("MESM_AUTOGRAPH_EVAL_MAX", "16"))
-        self.eval_captures = self.eval_replays = self.eval_eager = 0
+        self.eval_graphs = GraphCache(int(os.environ.get("MESM_AUTOGRAPH_EVAL_MAX", "16")))  # EvalGraphedStep
+        self.eval_eager = 0   # evaluation calls that ran eagerly
         self.eval_neg = None  # the draw of an eval call that ends up eager after all (it has been made already)
+
+    captures = property(lambda self: self.train_graphs.captures)
+    replays = property(lambda self: self.train_graphs.replays)
+    bad = property(lambda self: self.train_graphs.bad)
+    eval_captures = property(lambda self: self.eval_graphs.captures)
+    eval_replays = property(lambda self: self.eval_graphs.replays)
 
     # ------------------------------------------------------------------ configuration
     def configure(self, enabled=None, pad=None, pairs=None, max_graphs=None, eval=None):
@@ -188,18 +189,16 @@ class AutoGraph:
         if pairs is not None:
             self.pairs = int(pairs)
         if max_graphs is not None:
-            self.max_graphs = int(max_graphs)
+            self.train_graphs.max_graphs = int(max_graphs)
         return self
 
     def note_criterion(self, crit):
         if self.crit is None or self.crit() is not crit:
             self.crit = weakref.ref(crit)
-            if self.steps:  # graphs captured with another criterion object: its weights / losses are baked in
-                self.steps.clear()
-                self.seen.clear()
-            if self.eval_steps:
-                self.eval_steps.clear()
-                self.eval_seen.clear()
+            # graphs captured with another criterion object: its weights / losses are baked in
+            self.train_graphs.drop()
+            self.eval_graphs.drop()
+            self.spec = self._spec_key = None
 
     # ------------------------------------------------------------------ forward
     @staticmethod
@@ -235,36 +234,39 @@ class AutoGraph:
             work["_words_mask"] = m
         return work
 
-    def _shaped(self, batch):
-        """the batch padded like StepCache pads it (device tensors stay on the device)"""
-        if self.pad is not None and "_words_mask" in batch:
-            from .graphed import StepCache
-            batch = dict(batch)
-            batch["_words_mask"] = StepCache._pad_dim1(batch["_words_mask"], self.pad[1])
-        if self.pad is not None:
-            from .graphed import StepCache
-            Lv, Lw = self.pad
-            if batch["video_feat"].shape[1] > Lv or batch["words_id"].shape[1] > Lw:
-                return None
-            b = dict(batch)
-            for k in StepCache.CLIP_KEYS:
-                if k in b:
-                    b[k] = StepCache._pad_dim1(b[k], Lv)
-            for k in StepCache.WORD_KEYS:
-                if k in b:
-                    b[k] = StepCache._pad_dim1(b[k], Lw)
-            batch = b
-        if self.pairs:
-            from .batching import pad_pairs
-            n = batch["video_feat"].shape[0]
-            batch = pad_pairs(batch, (n + self.pairs - 1) // self.pairs * self.pairs)
-        return batch
+    def _prepare(self, model, batch, dataset_name, crit, train):
+        """what both paths do before they look for a graph -> (shaped batch, its host half or None, bucket key, group bucket),
+        or None: this call runs eagerly (a batch beyond `pad`, or anything the host half cannot handle).  The shaped batch is
+        padded like StepCache pads (device tensors stay on the device).  The host half comes from the collate's host copies
+        (counted in `host_side` for training) or from one fetch; the training path makes none before a criterion is known."""
+        try:
+            work = None
+            fetch = crit is not None or not train
+            if fetch:
+                if self._spec_key != (dataset_name, id(crit)):
+                    from .hostplan import HostSpec
+                    self.spec, self._spec_key = HostSpec.from_model(model, crit, dataset_name), (dataset_name, id(crit))
+                work = self._with_host_side(batch, self.spec)
+            if work is not None:
+                # the collate kept the host copies: no transfer back, no synchronisation in front of the forward launch
+                if train:
+                    self.host_side += 1
+                shaped = host = shape_batch(work, self.pad, self.pairs)
+            else:
+                shaped = shape_batch({k: v for k, v in batch.items() if k != "_host"}, self.pad, self.pairs)
+                host = None
+                if fetch:
+                    from .graphed import GraphedStep
+                    host = self.fetch(shaped, self.spec, GraphedStep.BIG)
+            key, gcap = self._key(model, shaped, dataset_name, None if host is None else host["num_clips"])
+        except Exception:
+            return None
+        return shaped, host, key, gcap
 
     @staticmethod
     def _key(model, batch, dataset_name, num_clips=None):
         n = batch["video_mask"].shape[0]
-        gmax = int((batch["num_clips"] if num_clips is None else num_clips).max())
-        gcap = next((c for c in GROUP_CAPS if c >= gmax), gmax)
+        gcap = group_bucket(batch["num_clips"] if num_clips is None else num_clips, GROUP_CAPS)
         sig = tuple(sorted(k for k, v in batch.items() if not k.startswith("_")))
         return (dataset_name, bool(model.training), n, tuple(batch["video_feat"].shape[1:]),
                 tuple(batch["words_id"].shape[1:]), gcap, "_n_real" in batch, sig), gcap
@@ -299,55 +301,34 @@ class AutoGraph:
             # built WITH the reducer (GraphedStep / StepCache(reducer=...)), not in a capture made behind its back
             return None
         crit = self.crit() if self.crit is not None else None
-        try:
-            host = None
-            if crit is not None and (self.spec is None or self.spec.dataset_name != dataset_name):
-                from .hostplan import HostSpec
-                self.spec = HostSpec.from_model(model, crit, dataset_name)
-            work = self._with_host_side(batch, self.spec) if crit is not None else None
-            if work is not None:
-                # the collate kept the host copies: no transfer back, no synchronisation in front of the forward launch
-                shaped = host = self._shaped(work)
-                self.host_side += 1
-            else:
-                shaped = self._shaped({k: v for k, v in batch.items() if k != "_host"})
-            if shaped is None:
-                return None
-            if crit is not None and host is None:
-                from .graphed import GraphedStep
-                host = self.fetch(shaped, self.spec, GraphedStep.BIG)
-            key, gcap = self._key(model, shaped, dataset_name, None if host is None else host["num_clips"])
-        except Exception:
+        got = self._prepare(model, batch, dataset_name, crit, train=True)
+        if got is None:
             return None
-        if key in self.bad:
+        shaped, host, key, gcap = got
+        cache = self.train_graphs
+        if key in cache.bad:
             return None
-        if crit is None or (key not in self.steps and self.seen.get(key, 0) < 1):
-            self.seen[key] = self.seen.get(key, 0) + 1
+        # (the visit counts without a criterion as well: the first step is the one the criterion introduces itself in)
+        if cache.first_visit(key) or crit is None:
             self.eager += 1
             return None
-        step = None
-        for s in self.steps.get(key, []):
-            try:
-                s.load_batch(shaped, redraw=True, host=host, defer_targets=True)
-            except ValueError:
-                continue
-            step = s
-            break
+        step = cache.find(key, lambda s: s.load_batch(shaped, redraw=True, host=host, defer_targets=True))
         if step is None:
-            step = self._capture(key, gcap, shaped, dataset_name, crit)
+            step = self._capture_train(key, gcap, shaped, dataset_name, crit)
             if step is None:
                 return None
-        else:
-            self.steps.move_to_end(key)
         out = step.forward_replay()
         if step._pending_targets is not None:
             try:
                 step.finish_targets()  # (the criterion's arrays, while the forward graph runs)
             except ValueError:
                 return None  # targets beyond the captured capacities: this step runs eagerly
-        self.replays += 1
+        cache.replays += 1
         n = batch["video_feat"].shape[0]
-        res = AutoOutputs(out if shaped["video_mask"].shape[0] == n else self._real_rows(out, n))
+        if shaped["video_mask"].shape[0] != n:  # a pair-padded replay: the caller's pairs (views)
+            from .graphed import map_tree
+            out = map_tree(lambda k, t: t[:n] if torch.is_tensor(t) and t.dim() >= 1 else t, out)
+        res = AutoOutputs(out)
         res._mesm_model = self.model
         res._auto_step, res._auto_gen, res._auto_batch = step, self.gen, batch
         return res
@@ -361,62 +342,45 @@ class AutoGraph:
         self.eval_neg = None
         model = self.model()
         crit = self.crit() if self.crit is not None else None
-        try:
-            if getattr(self, "_eval_spec_key", None) != (dataset_name, id(crit)):
-                from .hostplan import HostSpec
-                self.eval_spec = HostSpec.from_model(model, crit, dataset_name)
-                self._eval_spec_key = (dataset_name, id(crit))
-            spec = self.eval_spec
-            with_crit = crit is not None and all(k in batch for k in self._TARGETS) \
-                and ("saliency_label" in batch or "clip_mask" in batch)
-            work = self._with_host_side(batch, spec)
-            if work is not None:
-                shaped = host = self._shaped(work)
-            else:
-                shaped = self._shaped({k: v for k, v in batch.items() if k != "_host"})
-                host = None
-            if shaped is None:
-                self.eval_eager += 1
-                return None
-            if host is None:
-                from .graphed import GraphedStep
-                host = self.fetch(shaped, spec, GraphedStep.BIG)
-            seen_key, gcap = self._key(model, shaped, dataset_name, host["num_clips"])
-            # (visits are counted per shape: the first call of an epoch may come before the criterion introduced itself)
-            key = seen_key + (with_crit,)
-        except Exception:
+        with_crit = crit is not None and all(k in batch for k in self._TARGETS) \
+            and ("saliency_label" in batch or "clip_mask" in batch)
+        got = self._prepare(model, batch, dataset_name, crit, train=False)
+        if got is None:
             self.eval_eager += 1
             return None
-        if key in self.eval_bad or (key not in self.eval_steps and self.eval_seen.get(seen_key, 0) < 1):
-            self.eval_seen[seen_key] = self.eval_seen.get(seen_key, 0) + 1
+        shaped, host, seen_key, gcap = got
+        key = seen_key + (with_crit,)
+        cache = self.eval_graphs
+        # (visits are counted per shape: the first call of an epoch may come before the criterion introduced itself)
+        first = cache.first_visit(key, seen_key)
+        if key in cache.bad or first:
             self.eval_eager += 1
             return None
         # the eager call's one host draw, here: same stream, same place in it (the real groups; padding pairs -> 0)
-        groups = [int(g) for g in host["num_clips"].tolist()]
-        n_real = shaped.get("_n_real")
-        neg = draws.neg_index(groups, n_real)
+        neg = draws.neg_index([int(g) for g in host["num_clips"].tolist()], shaped.get("_n_real"))
         n = batch["video_feat"].shape[0]
         self.eval_neg = neg[:n]
-        step = None
-        for s in self.eval_steps.get(key, []):
-            try:
-                s._draws = (neg, None)
-                s.load_batch(shaped, redraw=False, host=host)
-            except ValueError:
-                continue
-            step = s
-            break
+
+        def load(s):
+            s._draws = (neg, None)
+            s.load_batch(shaped, redraw=False, host=host)
+        step = cache.find(key, load)
         if step is None:
-            step = self._capture_eval(key, gcap, shaped, dataset_name, crit if with_crit else None, neg)
+            from .graphed import EvalGraphedStep, capture_batch
+
+            def capture():
+                s = EvalGraphedStep(model, crit if with_crit else None, capture_batch(shaped, shaped["video_feat"].device),
+                                    dataset_name, warmup=1, caps="auto", group_cap=gcap if gcap > 1 else None, neg_index=neg)
+                self._check_eval_axes(model, s, shaped)
+                return s
+            step = self._capture(cache, key, capture, "eval capture")
             if step is None:
                 self.eval_eager += 1
                 return None
-        else:
-            self.eval_steps.move_to_end(key)
         buf = step.replay()
         out, losses, total = step.unpack(buf)
         self.eval_neg = None
-        self.eval_replays += 1
+        cache.replays += 1
         res = AutoOutputs(self._eval_extents(model, out, batch, n))
         res._mesm_model = self.model
         res._auto_batch = batch
@@ -454,6 +418,7 @@ class AutoGraph:
     @staticmethod
     def _eval_extents(model, out, batch, n):
         """outputs of a padded replay with the eager call's shapes: the real pairs, the caller's clips and words (views)"""
+        from .graphed import map_tree
         Lv, Lw = AutoGraph._extents(model, batch)
 
         def cut(k, t):
@@ -466,8 +431,7 @@ class AutoGraph:
                 elif k in _EVAL_WORD_OUT:
                     t = t[:, :Lw + _EVAL_WORD_OUT[k]]
             return t
-        return {k: ([{kk: cut(kk, vv) for kk, vv in d.items()} for d in v] if isinstance(v, list) else cut(k, v))
-                for k, v in out.items()}
+        return map_tree(cut, out)
 
     def eval_criterion(self, crit, outputs, targets, is_training):
         """the losses captured with a replayed evaluation forward, or None (the caller runs the eager criterion)"""
@@ -479,85 +443,35 @@ class AutoGraph:
         losses, total = outputs._eval_losses
         return dict(losses), total
 
-    def _capture_eval(self, key, gcap, batch, dataset_name, crit, neg):
-        from .graphed import EvalGraphedStep
-        model = self.model()
-        while sum(len(v) for v in self.eval_steps.values()) >= self.eval_max_graphs and self.eval_steps:
-            self.eval_steps.popitem(last=False)
+    def _capture(self, cache, key, capture, what="capture"):
+        """cache.add(key, capture) with the model's forward reserved for the capture; a bucket whose capture fails stays
+        eager (said once) -> the new step or None"""
         self.busy = True
         try:
-            step = EvalGraphedStep(model, crit, self._static(batch), dataset_name, warmup=1, caps="auto",
-                                   group_cap=gcap if gcap > 1 else None, neg_index=neg)
-            self._check_eval_axes(model, step, batch)
-        except Exception as e:
-            self.eval_bad.add(key)
-            warnings.warn("mesm_amd.autograph: eval capture failed for %r (%s: %s); this shape stays eager"
-                          % (key, type(e).__name__, e))
-            step = None
+            return cache.add(key, capture)
+        except Exception as e:  # a shape this build cannot capture: stay eager for it, say so once
+            cache.bad.add(key)
+            warnings.warn("mesm_amd.autograph: %s failed for %r (%s: %s); this shape stays eager" % (what, key, type(e).__name__, e))
+            return None
         finally:
             self.busy = False
-        if step is None:
-            return None
-        self.eval_steps.setdefault(key, []).append(step)
-        self.eval_captures += 1
-        return step
 
-    @staticmethod
-    def _static(batch):
-        """the capture's own copy of a (shaped) device batch: big tensors padded to the pair extent on the device"""
-        clone = lambda v: v.clone() if torch.is_tensor(v) else v
-        static = {}
-        for k, v in batch.items():
-            if k == "_n_real":
-                continue
-            if isinstance(v, list) and v and isinstance(v[0], dict):
-                static[k] = [{kk: clone(vv) for kk, vv in d.items()} for d in v]
-            else:
-                static[k] = clone(v)
-        if "_n_real" in batch:
-            static["_n_real"] = batch["_n_real"]
-            P = static["video_mask"].shape[0]
-            for kk in ("video_feat", "words_id"):
-                t = static[kk]
-                if t.shape[0] < P:
-                    static[kk] = torch.cat([t, t[:1].expand((P - t.shape[0],) + tuple(t.shape[1:]))]).contiguous()
-        return static
-
-    @staticmethod
-    def _real_rows(out, n):
-        """outputs of a pair-padded replay, cut back to the caller's pairs (views; every entry leads with the pair axis)"""
-        cut = lambda t: t[:n] if torch.is_tensor(t) and t.dim() >= 1 else t
-        return {k: ([{kk: cut(vv) for kk, vv in d.items()} for d in v] if isinstance(v, list) else cut(v))
-                for k, v in out.items()}
-
-    def _capture(self, key, gcap, batch, dataset_name, crit):
-        from .graphed import SplitGraphedStep
+    def _capture_train(self, key, gcap, batch, dataset_name, crit):
+        from .graphed import SplitGraphedStep, capture_batch
         model = self.model()
         gb = model.gradbuf()
-        while sum(len(v) for v in self.steps.values()) >= self.max_graphs and self.steps:
-            self.steps.popitem(last=False)
-        static = self._static(batch)
         # the warm-up and capture steps run real backward passes: the caller's gradients are put back afterwards
         had = [p.grad is not None for p in gb.params]
         saved = gb.flat.clone() if (gb.flat is not None and any(had)) else None
-        self.busy = True
         try:
-            step = SplitGraphedStep(model, crit, static, dataset_name, warmup=1, caps="auto", group_cap=gcap if gcap > 1 else None)
-        except Exception as e:  # a shape this build cannot capture: stay eager for it, say so once
-            self.bad.add(key)
-            warnings.warn("mesm_amd.autograph: capture failed for %r (%s: %s); this shape stays eager" % (key, type(e).__name__, e))
-            step = None
+            return self._capture(self.train_graphs, key, lambda: SplitGraphedStep(
+                model, crit, capture_batch(batch, batch["video_feat"].device), dataset_name, warmup=1, caps="auto",
+                group_cap=gcap if gcap > 1 else None))
         finally:
-            self.busy = False
             if saved is not None:
                 gb.flat.copy_(saved)
             for p, h in zip(gb.params, had):
                 p.grad = p._mesm_gview if h else None
-        if step is None:
-            return None
-        self.steps.setdefault(key, []).append(step)
-        self.captures += 1
-        return step
 
     # ------------------------------------------------------------------ criterion / backward
     def _check(self, step, gen, what):

@@ -269,3 +269,58 @@ def pad_pairs(batch, P, big=1 << 20):
         elif isinstance(v, (list, tuple)) and len(v) == N:
             out[key] = list(v) + [v[0]] * k
     return out
+
+
+# ---- the shapes a captured step takes (graphed.StepCache, loader.HostPipeline, autograph.AutoGraph)
+# batch entries with a clip / word axis at dim 1
+CLIP_KEYS = ("video_feat", "video_mask", "clip_mask", "saliency_label")
+WORD_KEYS = ("words_id", "words_mask", "words_weight", "unknown_mask", "words_label")
+
+
+def round_up(x, m):
+    return (x + m - 1) // m * m
+
+
+def pad_dim1(t, L):
+    """t zero-padded along dim 1 to L (as it is when not a tensor of at least 2 dims, or when it is that long already)"""
+    if not torch.is_tensor(t) or t.dim() < 2 or t.shape[1] >= L:
+        return t
+    out = t.new_zeros((t.shape[0], L) + tuple(t.shape[2:]))
+    out[:, :t.shape[1]] = t
+    return out
+
+
+def shape_batch(batch, pad=None, pairs=None):
+    """The batch as a bucketed graph takes it: the clip / word axes zero-padded to pad=(Lv, Lw) (masked positions, what the
+    reference's own collate does up to the batch maximum; ValueError when an extent exceeds `pad`), then the pair axis padded
+    to the next multiple of `pairs` (pad_pairs).  A new dict when anything is padded, tensors shared where nothing is; host
+    or device tensors.  The word-validity mask an AutoGraph batch carries (`_words_mask`) is padded with the words."""
+    if pad is not None:
+        Lv, Lw = pad
+        if batch["video_feat"].shape[1] > Lv or batch["words_id"].shape[1] > Lw:
+            raise ValueError("batch extents (%d clips, %d words) exceed pad=%r"
+                             % (batch["video_feat"].shape[1], batch["words_id"].shape[1], pad))
+        batch = dict(batch)
+        for keys, L in ((CLIP_KEYS, Lv), (WORD_KEYS + ("_words_mask",), Lw)):
+            for k in keys:
+                if k in batch:
+                    batch[k] = pad_dim1(batch[k], L)
+    if pairs:
+        batch = pad_pairs(batch, round_up(batch["video_feat"].shape[0], pairs))
+    return batch
+
+
+def group_bucket(num_clips, caps):
+    """the smallest of the ascending group-size buckets `caps` that holds the largest video group (beyond the last bucket:
+    the largest group itself)"""
+    gmax = int(num_clips.max())
+    return next((c for c in caps if c >= gmax), gmax)
+
+
+def bucket_key(batch, group_caps=None):
+    """the graph bucket of a shaped batch (graphed.StepCache, loader.HostPipeline): ((pairs, clips, Dv), (pairs, words[, Dt]))
+    plus, with `group_caps`, the group bucket.  The pair extent comes from a mask: the big feature tensors of a pair-padded
+    host batch keep their real rows only."""
+    n = batch["video_mask"].shape[0]
+    key = ((n,) + tuple(batch["video_feat"].shape[1:]), (n,) + tuple(batch["words_id"].shape[1:]))
+    return key + (group_bucket(batch["num_clips"], group_caps),) if group_caps else key

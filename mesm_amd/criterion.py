@@ -75,6 +75,13 @@ def loss_entries(lv, index):
     return {n: LossEntry(lv[i], pack, i) for n, i in index.items()}
 
 
+def loss_pack(losses):
+    """the ONE loss vector pack whose elements all entries of `losses` are (loss_entries), or None"""
+    vals = list(losses.values())
+    pack = getattr(vals[0], "_pack", None) if vals else None
+    return pack if pack is not None and all(getattr(v, "_pack", None) is pack for v in vals) else None
+
+
 class TargetPlan:
     """Flattened targets + host-built index tensors (built once per batch, reused for the aux
     decoder layers): tgt_cxw / tgt_xx (sumT, 2), tgt_off (N+1) int32, Tmax, group_mask (N, N) bool (True where two

@@ -28,16 +28,39 @@ The captured launches bake in the addresses of the parameters: they must not mov
 raises if an address differs from capture time.
 """
 import os
+from collections import OrderedDict
 
 import torch
 
 from . import draws
 from . import kernels as kn
-from .criterion import TargetPlan
+from .batching import bucket_key, shape_batch
+from .criterion import TargetPlan, loss_pack
 
 
-def _round_up(x, m):
-    return (x + m - 1) // m * m
+def map_tree(fn, tree):
+    """{k: fn(k, v)} over a batch or an output dict, into its lists of dicts (per-pair targets, aux_outputs): fn(inner key,
+    value) there.  fn sees every value, tensor or not."""
+    return {k: ([{kk: fn(kk, vv) for kk, vv in d.items()} for d in v] if isinstance(v, list) and v and isinstance(v[0], dict)
+                else fn(k, v)) for k, v in tree.items()}
+
+
+def capture_batch(batch, device):
+    """the capture's own copy of a shaped batch: every tensor copied to `device` (words_weight stays where it is, as
+    prepare_batch_input leaves it; a tensor already there is cloned); the big feature tensors of a pair-padded batch, which
+    keep their real rows only (batching.pad_pairs), padded to the pair extent on the device"""
+    def copy(k, v):
+        if not torch.is_tensor(v):
+            return v
+        return v.clone() if k == "words_weight" else v.to(device, copy=True)
+    static = map_tree(copy, batch)
+    if "_n_real" in batch:
+        P = static["video_mask"].shape[0]
+        for k in ("video_feat", "words_id"):
+            t = static[k]
+            if t.shape[0] < P:
+                static[k] = torch.cat([t, t[:1].expand((P - t.shape[0],) + tuple(t.shape[1:]))]).contiguous()
+    return static
 
 
 _CAPTURE_STREAMS = {}
@@ -266,14 +289,8 @@ class GraphedStep:
         copy each.  redraw: also draw new negatives / MLM words here (then call run(redraw=False): one upload per
         step instead of two).  Raises ValueError (nothing is modified) when it does not fit."""
         groups = [int(g) for g in (batch if host is None else host)["num_clips"].tolist()]
-        if groups != self._groups and (self.caps.get("M") is None or sum(groups) != sum(self._groups)):
-            # exact-extent graphs (caps=None) are tied to their grouping; with capacities any grouping of the
-            # same number of pairs fits as long as its largest group does (checked by the plan below)
-            raise ValueError("GraphedStep.load_batch: group sizes changed %s -> %s" % (self._groups, groups))
         n_real = batch.get("_n_real")
-        if (n_real is None) != (self._n_real is None):
-            raise ValueError("GraphedStep.load_batch: the step was captured %s a device-side pair count"
-                             % ("with" if self._n_real is not None else "without"))
+        self._check_fits(groups, n_real)
         old_groups, self._groups = self._groups, groups
         old_real, self._n_real = self._n_real, n_real
         try:
@@ -315,10 +332,7 @@ class GraphedStep:
             # until then the arena image keeps the previous batch's (they are not part of this upload)
             arr.update({k: v for k, v in self._arr.items() if k.startswith("t.")})
             self._pending_targets = host
-        for k in ("vid_identity", "has_vid_src"):
-            if pmeta.get(k) != self._pmeta.get(k):
-                raise ValueError("GraphedStep.load_batch: plan.%s changed (%r -> %r): needs its own graph"
-                                 % (k, self._pmeta.get(k), pmeta.get(k)))
+        self._check_fits(self._groups, self._n_real, pmeta)  # (groups and pair count: checked by load_batch)
         self.arena.check(arr)
         # nothing above modified anything; from here on only copies
         self._arr = arr
@@ -348,6 +362,20 @@ class GraphedStep:
 
     _pending_targets = None
 
+    def _check_fits(self, groups, n_real, pmeta=None):
+        """ValueError unless a batch of these group sizes, this pair-count mode and (given) this plan meta fits the graph"""
+        if groups != self._groups and (self.caps.get("M") is None or sum(groups) != sum(self._groups)):
+            # exact-extent graphs (caps=None) are tied to their grouping; with capacities any grouping of the
+            # same number of pairs fits as long as its largest group does (checked by the plan)
+            raise ValueError("%s: group sizes changed %s -> %s" % (type(self).__name__, self._groups, groups))
+        if (n_real is None) != (self._n_real is None):
+            raise ValueError("%s: the step was captured %s a device-side pair count"
+                             % (type(self).__name__, "with" if self._n_real is not None else "without"))
+        for k in ("vid_identity", "has_vid_src"):
+            if pmeta is not None and pmeta.get(k) != self._pmeta.get(k):
+                raise ValueError("%s: plan.%s changed (%r -> %r): needs its own graph"
+                                 % (type(self).__name__, k, self._pmeta.get(k), pmeta.get(k)))
+
     def finish_targets(self):
         """second half of load_batch(defer_targets=True): the criterion's flattened targets, built and uploaded while the
         forward graph runs.  Raises ValueError when they do not fit the captured capacities (the caller then runs the step
@@ -370,17 +398,9 @@ class GraphedStep:
         if prep["spec"] != self.spec:
             raise ValueError("GraphedStep.load_prepared: prepared for another model configuration")
         groups = prep["groups"]
-        if groups != self._groups and (self.caps.get("M") is None or sum(groups) != sum(self._groups)):
-            raise ValueError("GraphedStep.load_prepared: group sizes changed %s -> %s" % (self._groups, groups))
-        if (prep["n_real"] is None) != (self._n_real is None):
-            raise ValueError("GraphedStep.load_prepared: pair-count mode differs from the captured step")
+        self._check_fits(groups, prep["n_real"], prep["pmeta"])
         if {k: prep["caps"].get(k) for k in self.caps} != self.caps:
             raise ValueError("GraphedStep.load_prepared: prepared with other capacities %r (graph: %r)" % (prep["caps"], self.caps))
-        pmeta, tmeta = prep["pmeta"], prep["tmeta"]
-        for k in ("vid_identity", "has_vid_src"):
-            if pmeta.get(k) != self._pmeta.get(k):
-                raise ValueError("GraphedStep.load_prepared: plan.%s changed (%r -> %r): needs its own graph"
-                                 % (k, self._pmeta.get(k), pmeta.get(k)))
         arr = {k: (v.numpy() if torch.is_tensor(v) else v) for k, v in prep["arr"].items()}
         self.arena.check(arr)
         big = prep["big"]
@@ -403,7 +423,7 @@ class GraphedStep:
             arr["p.masked_words"] = mw
         self._arr, self._draws = arr, (neg, mw)
         self.arena.upload(arr)
-        self.tplan.sizes, self.tplan.sumT = tmeta["sizes"], tmeta["sumT"]
+        self.tplan.sizes, self.tplan.sumT = prep["tmeta"]["sizes"], prep["tmeta"]["sumT"]
         for k, v in big.items():
             self._stage_big(k, self.batch[k], v)
         self._turn ^= 1
@@ -466,6 +486,18 @@ class GraphedStep:
             self._arr["p.masked_words"] = mw
         self.arena.upload(self._arr)
 
+    def _check_addresses(self):
+        """the address comparison of run() (273 addresses: 0.1 ms of the caller's critical path) only when the model says
+        tensors may have moved (MESM._apply / a re-flattening bump _addr_gen); the two flat buffers' addresses every time"""
+        m = self.model
+        gen = m.__dict__.get("_addr_gen", 0)
+        fp = m._flat_params
+        quick = (fp.data_ptr() if fp is not None else 0, m.gradbuf().flat.data_ptr())
+        if gen != getattr(self, "_addr_gen", None) or quick != getattr(self, "_quick_ptrs", None):
+            if self._param_ptrs() != self._ptrs:
+                raise RuntimeError("%s: a parameter or the gradient buffer moved after capture" % type(self).__name__)
+            self._addr_gen, self._quick_ptrs = gen, quick
+
     def run(self, redraw=True):
         if self._param_ptrs() != self._ptrs:
             raise RuntimeError(
@@ -510,33 +542,19 @@ class SplitGraphedStep(GraphedStep):
             total.backward(self.seed)
         gb = self.model.gradbuf()
         self.grad_params = [p for p in gb.params if p.grad is not None]
-        det = lambda t: t.detach() if torch.is_tensor(t) else t
-        self.out = {k: ([{kk: det(vv) for kk, vv in d.items()} for d in v] if isinstance(v, list) else det(v))
-                    for k, v in out.items()}
+        self.out = map_tree(lambda k, t: t.detach() if torch.is_tensor(t) else t, out)
         self.total = total.detach()
-        vals = list(losses.values())
         # the loss entries are elements of ONE vector (criterion.loss_entries): a replay hands out a copy of it, one launch
-        pack = getattr(vals[0], "_pack", None) if vals else None
-        same = pack is not None and all(getattr(v, "_pack", None) is pack for v in vals)
-        self.loss_vec = pack.vec.detach() if same else None
-        self.loss_index = {k: int(v._i) for k, v in losses.items()} if same else None
+        pack = loss_pack(losses)
+        self.loss_vec = pack.vec.detach() if pack is not None else None
+        self.loss_index = {k: int(v._i) for k, v in losses.items()} if pack is not None else None
         self.losses = {k: v.detach() for k, v in losses.items()}
 
     def run(self, redraw=True):
         raise RuntimeError("SplitGraphedStep is replayed in three parts (forward_replay / criterion_replay / backward_replay)")
 
     def forward_replay(self):
-        # the 273-address comparison of GraphedStep.run costs 0.1 ms of the caller's critical path: here it runs when the
-        # model says tensors may have moved (MESM._apply / a re-flattening bump _addr_gen), and the two flat buffers'
-        # addresses are compared every time
-        m = self.model
-        gen = m.__dict__.get("_addr_gen", 0)
-        fp = m._flat_params
-        quick = (fp.data_ptr() if fp is not None else 0, m.gradbuf().flat.data_ptr())
-        if gen != getattr(self, "_addr_gen", None) or quick != getattr(self, "_quick_ptrs", None):
-            if self._param_ptrs() != self._ptrs:
-                raise RuntimeError("SplitGraphedStep: a parameter or the gradient buffer moved after capture")
-            self._addr_gen, self._quick_ptrs = gen, quick
+        self._check_addresses()
         self.g_fwd.replay()
         return self.out
 
@@ -608,9 +626,8 @@ class EvalGraphedStep(GraphedStep):
                 items.append((k, v))
         self.loss_index = None
         if losses is not None:
-            vals = list(losses.values())
-            pack = getattr(vals[0], "_pack", None) if vals else None
-            if pack is not None and all(getattr(v, "_pack", None) is pack for v in vals):
+            pack = loss_pack(losses)
+            if pack is not None:
                 items.append((("_loss_vec",), pack.vec))
                 self.loss_index = {k: int(v._i) for k, v in losses.items()}
             else:
@@ -632,14 +649,7 @@ class EvalGraphedStep(GraphedStep):
 
     def replay(self):
         """replay the captured call on the loaded batch and draws; -> a fresh copy of its pack (caller-owned memory)"""
-        m = self.model
-        gen = m.__dict__.get("_addr_gen", 0)
-        fp = m._flat_params
-        quick = (fp.data_ptr() if fp is not None else 0, m.gradbuf().flat.data_ptr())
-        if gen != getattr(self, "_addr_gen", None) or quick != getattr(self, "_quick_ptrs", None):
-            if self._param_ptrs() != self._ptrs:
-                raise RuntimeError("EvalGraphedStep: a parameter moved after capture")
-            self._addr_gen, self._quick_ptrs = gen, quick
+        self._check_addresses()
         self.graph.replay()
         return self.pack.clone()
 
@@ -670,18 +680,62 @@ class EvalGraphedStep(GraphedStep):
         raise RuntimeError("EvalGraphedStep is replayed with replay() / unpack()")
 
 
-class StepCache:
+class GraphCache:
+    """Captured steps by bucket key, for StepCache and both paths of autograph.AutoGraph: key -> [steps] (a bucket can need
+    more than one graph: other plan switches, capacities the first one lacks), at most `max_graphs` GRAPHS in all, the least
+    recently used key evicted first (a hit refreshes it).  `captures` / `replays` count for the owner; `seen` (the bucket
+    shapes visited) and `bad` (keys whose capture failed) are autograph.AutoGraph's bookkeeping."""
+
+    def __init__(self, max_graphs=16):
+        self.steps = OrderedDict()
+        self.max_graphs = max_graphs
+        self.seen = set()
+        self.bad = set()
+        self.captures = 0
+        self.replays = 0
+
+    def find(self, key, load):
+        """the first step of bucket `key` that load(step) takes (ValueError: the batch does not fit it), or None"""
+        for s in self.steps.get(key, ()):
+            try:
+                load(s)
+            except ValueError:
+                continue
+            self.steps.move_to_end(key)
+            return s
+        return None
+
+    def add(self, key, capture):
+        """evict until one more graph fits the budget, then capture() -> a new step of bucket `key`"""
+        while self.steps and sum(len(v) for v in self.steps.values()) >= self.max_graphs:
+            self.steps.popitem(last=False)
+        step = capture()
+        self.steps.setdefault(key, []).append(step)
+        self.captures += 1
+        return step
+
+    def first_visit(self, key, shape=None):
+        """count a visit of bucket `key` (visits are counted per `shape`, default the key): True on the first one of a key
+        without graphs -- it runs eagerly, the next one captures"""
+        shape = key if shape is None else shape
+        first = key not in self.steps and shape not in self.seen
+        self.seen.add(shape)
+        return first
+
+    def drop(self):
+        """forget the graphs and the visits that led to them (they were captured with another criterion object)"""
+        if self.steps:
+            self.steps.clear()
+            self.seen.clear()
+
+
+class StepCache(GraphCache):
     """One captured graph per batch-shape bucket: `run(batch)` replays a graph whose shape key
     (N, Lv, Lw, feature dims) and capture-time capacities (largest video group, GT-clip count, group video
     length, target windows) fit the batch, capturing a new one when none does.  `pad=(Lv_cap, Lw_cap)` first
-    pads every batch to fixed clip / word extents (masked positions, what the reference's own collate does up to
-    the batch maximum), so that the key is the number of pairs alone: real loaders emit a different (N, Lv, Lw,
-    grouping) almost every batch -- items are videos with all their queries, dataset/base.py:164-207 -- and
-    only a handful of distinct N.  `captures` counts the graphs built."""
-
-    # batch entries with a clip / word axis at dim 1
-    CLIP_KEYS = ("video_feat", "video_mask", "clip_mask", "saliency_label")
-    WORD_KEYS = ("words_id", "words_mask", "words_weight", "unknown_mask", "words_label")
+    pads every batch to fixed clip / word extents (batching.shape_batch), so that the key is the number of pairs alone:
+    real loaders emit a different (N, Lv, Lw, grouping) almost every batch -- items are videos with all their queries,
+    dataset/base.py:164-207 -- and only a handful of distinct N.  `captures` counts the graphs built."""
 
     def __init__(self, model, criterion, dataset_name, reducer=None, max_graphs=16, pad=None, pairs=None,
                  group_caps=None):
@@ -693,82 +747,23 @@ class StepCache:
         video groups of up to the smallest bucket that holds its largest group (9 = the QVHighlights maximum), so that
         (pair bucket, group bucket) alone decide which graph a batch replays -- groups cost SS-MESM key slots
         (group size x clips per pair), which is why there is more than one bucket."""
+        super().__init__(max_graphs)
         self.model, self.crit, self.dataset_name = model, criterion, dataset_name
         self.reducer = reducer
-        self.steps = {}
-        self.max_graphs = max_graphs
         self.pad = pad
         self.pairs = pairs
         self.group_caps = tuple(sorted(group_caps)) if group_caps else None
-        self.captures = 0
-        self.replays = 0
-
-    @staticmethod
-    def key(batch):
-        # (the pair extent from a mask: big feature tensors of a pair-padded batch arrive with their real rows only)
-        n = batch["video_mask"].shape[0]
-        return ((n,) + tuple(batch["video_feat"].shape[1:]), (n,) + tuple(batch["words_id"].shape[1:]))
-
-    @staticmethod
-    def _pad_dim1(t, L):
-        if t is None or not torch.is_tensor(t) or t.dim() < 2 or t.shape[1] >= L:
-            return t
-        out = t.new_zeros((t.shape[0], L) + tuple(t.shape[2:]))
-        out[:, :t.shape[1]] = t
-        return out
-
-    def padded(self, batch):
-        """the batch with its clip / word axes zero-padded to `pad` (new dict; tensors shared when nothing to do)"""
-        if self.pad is None:
-            return batch
-        Lv, Lw = self.pad
-        if batch["video_feat"].shape[1] > Lv or batch["words_id"].shape[1] > Lw:
-            raise ValueError("StepCache: batch extents (%d clips, %d words) exceed pad=%r"
-                             % (batch["video_feat"].shape[1], batch["words_id"].shape[1], self.pad))
-        b = dict(batch)
-        for k in self.CLIP_KEYS:
-            if k in b:
-                b[k] = self._pad_dim1(b[k], Lv)
-        for k in self.WORD_KEYS:
-            if k in b:
-                b[k] = self._pad_dim1(b[k], Lw)
-        return b
 
     def run(self, batch, redraw=True):
-        batch = self.padded(batch)
-        if self.pairs:
-            from .batching import pad_pairs
-            n = batch["video_feat"].shape[0]
-            batch = pad_pairs(batch, _round_up(n, self.pairs))
-        k = self.key(batch)
-        gcap = None
-        if self.group_caps:
-            gmax = int(batch["num_clips"].max())
-            gcap = next((c for c in self.group_caps if c >= gmax), gmax)
-            k = k + (gcap,)
-        for gs in self.steps.get(k, []):
-            try:
-                gs.load_batch(batch, redraw=redraw)
-            except ValueError:
-                continue
+        batch = shape_batch(batch, self.pad, self.pairs)
+        k = bucket_key(batch, self.group_caps)
+        gs = self.find(k, lambda s: s.load_batch(batch, redraw=redraw))
+        if gs is not None:
             self.replays += 1
             return gs.run(redraw=False), gs
-        if sum(len(v) for v in self.steps.values()) >= self.max_graphs:
-            self.steps.pop(next(iter(self.steps)))
-        from .synthetic import to_device
-        static = to_device({kk: (v.clone() if torch.is_tensor(v) else v) for kk, v in batch.items() if kk != "_n_real"},
-                           next(self.model.parameters()).device)
-        if "_n_real" in batch:
-            static["_n_real"] = batch["_n_real"]
-            P = static["video_mask"].shape[0]
-            for kk in ("video_feat", "words_id"):  # big tensors arrive with their real rows: pad on the device
-                t = static[kk]
-                if t.shape[0] < P:
-                    static[kk] = torch.cat([t, t[:1].expand((P - t.shape[0],) + tuple(t.shape[1:]))]).contiguous()
-        gs = GraphedStep(self.model, self.crit, static, self.dataset_name, warmup=1, reducer=self.reducer,
-                         caps="auto", group_cap=gcap)
-        self.steps.setdefault(k, []).append(gs)
-        self.captures += 1
+        dev = next(self.model.parameters()).device
+        gs = self.add(k, lambda: GraphedStep(self.model, self.crit, capture_batch(batch, dev), self.dataset_name, warmup=1,
+                                             reducer=self.reducer, caps="auto", group_cap=k[2] if self.group_caps else None))
         return gs.run(redraw=redraw), gs
 
     def pipeline(self, keep_raw=True):
@@ -783,11 +778,8 @@ class StepCache:
         """`run` for a batch prepared by a loader worker (loader.HostPipeline.prepare): the graph of its bucket key takes
         the arrays as they are (the two host draws are made here); a bucket without a graph yet goes through `run` on
         the raw batch the worker kept alongside (prep["raw"]), which captures it."""
-        for gs in self.steps.get(prep["key"], []):
-            try:
-                gs.load_prepared(prep)
-            except ValueError:
-                continue
+        gs = self.find(prep["key"], lambda s: s.load_prepared(prep))
+        if gs is not None:
             self.replays += 1
             return gs.run(redraw=False), gs
         if prep.get("raw") is None:

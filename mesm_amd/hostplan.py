@@ -11,9 +11,7 @@ The two host-RNG draws of the reference's forward (negative query index, masked-
 import numpy as np
 import torch
 
-
-def _round_up(x, m):
-    return (x + m - 1) // m * m
+from .batching import round_up
 
 
 class HostSpec:
@@ -78,7 +76,7 @@ class HostSpec:
             caps = {}
             N, Lv = batch["video_mask"].shape
             if self.rec_fw:
-                caps["Lc"] = Lv if group_cap else min(Lv, _round_up(int(batch["clip_mask"].sum(1).max()), 8))
+                caps["Lc"] = Lv if group_cap else min(Lv, round_up(int(batch["clip_mask"].sum(1).max()), 8))
             gmax = max(max(groups), group_cap or 0)
             if self.rec_ss:
                 caps["M"] = gmax  # sentence slots per pair (SS branch): other groupings with <= M fit
@@ -87,7 +85,7 @@ class HostSpec:
                 lens = [int(c.sum()) for c in torch.split(vm, groups)]
                 full = all(g == 1 for g in groups) and bool(vm.all()) and not group_cap
                 # 64 = one key tile of the attention kernels; a group cannot hold more than its pairs' clips
-                caps["Lss"] = Lv if full else (gmax * Lv if group_cap else min(_round_up(max(lens), 64), gmax * Lv))
+                caps["Lss"] = Lv if full else (gmax * Lv if group_cap else min(round_up(max(lens), 64), gmax * Lv))
             if self.multi_clip:
                 Q = self.num_queries
                 tmax = max(len(t["spans"]) for t in batch["norm_span"])

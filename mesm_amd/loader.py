@@ -22,18 +22,17 @@ import collections
 import numpy as np
 import torch
 
-from .hostplan import HostSpec, _round_up
+from .batching import bucket_key, round_up, shape_batch
+from .hostplan import HostSpec
 
 
 class HostPipeline:
     """StepCache's host half, picklable.  prepare(raw collated host batch) -> prepared dict:
-       key      bucket key of the graph that serves it (StepCache.key + group bucket)
+       key      bucket key of the graph that serves it (batching.bucket_key, as StepCache.run computes it)
        arr      {name: tensor} arena content (placeholder draws), pmeta / tmeta, wm (word validity), caps
        big      {video_feat, words_id}: the real rows, padded to the fixed clip / word extents
        groups, n_real, num_clips, words_weight
        raw      the raw batch when keep_raw (a bucket's first batch has to go through StepCache.run to be captured)"""
-    CLIP_KEYS = ("video_feat", "video_mask", "clip_mask", "saliency_label")
-    WORD_KEYS = ("words_id", "words_mask", "words_weight", "unknown_mask", "words_label")
     BIG = 1 << 20
 
     def __init__(self, spec, pad=None, pairs=None, group_caps=None, keep_raw=True):
@@ -42,42 +41,11 @@ class HostPipeline:
         self.group_caps = tuple(sorted(group_caps)) if group_caps else None
         self.keep_raw = keep_raw
 
-    @staticmethod
-    def _pad_dim1(t, L):
-        if t is None or not torch.is_tensor(t) or t.dim() < 2 or t.shape[1] >= L:
-            return t
-        out = t.new_zeros((t.shape[0], L) + tuple(t.shape[2:]))
-        out[:, :t.shape[1]] = t
-        return out
-
-    def padded(self, batch):
-        if self.pad is None:
-            return batch
-        Lv, Lw = self.pad
-        if batch["video_feat"].shape[1] > Lv or batch["words_id"].shape[1] > Lw:
-            raise ValueError("HostPipeline: batch extents (%d clips, %d words) exceed pad=%r"
-                             % (batch["video_feat"].shape[1], batch["words_id"].shape[1], self.pad))
-        b = dict(batch)
-        for k in self.CLIP_KEYS:
-            if k in b:
-                b[k] = self._pad_dim1(b[k], Lv)
-        for k in self.WORD_KEYS:
-            if k in b:
-                b[k] = self._pad_dim1(b[k], Lw)
-        return b
-
     def prepare(self, raw):
-        from .batching import pad_pairs
-        batch = self.padded(raw)
-        if self.pairs:
-            batch = pad_pairs(batch, _round_up(batch["video_feat"].shape[0], self.pairs))
+        batch = shape_batch(raw, self.pad, self.pairs)
+        key = bucket_key(batch, self.group_caps)
+        gcap = key[2] if self.group_caps else None
         n = batch["video_mask"].shape[0]
-        key = ((n,) + tuple(batch["video_feat"].shape[1:]), (n,) + tuple(batch["words_id"].shape[1:]))
-        gcap = None
-        if self.group_caps:
-            gmax = int(batch["num_clips"].max())
-            gcap = next((c for c in self.group_caps if c >= gmax), gmax)
-            key = key + (gcap,)
         groups = [int(g) for g in batch["num_clips"].tolist()]
         n_real = batch.get("_n_real")
         host = {k: v for k, v in batch.items() if torch.is_tensor(v)}
@@ -86,10 +54,9 @@ class HostPipeline:
                 host[k] = batch[k]
         caps = self.spec.resolve_caps("auto", batch, groups, gcap)
         # placeholder draws: the training process draws (the reference's RNG stream lives there)
-        N = n
-        neg0 = torch.zeros(N, dtype=torch.int64).numpy()
+        neg0 = torch.zeros(n, dtype=torch.int64).numpy()
         wm = self.spec.words_mask(host)
-        mw0 = torch.zeros((N, wm.shape[1]), dtype=torch.bool).numpy() if self.spec.rec_fw else None
+        mw0 = torch.zeros((n, wm.shape[1]), dtype=torch.bool).numpy() if self.spec.rec_fw else None
         arr, pmeta, tmeta, wm = self.spec.host_arrays(host, groups, caps, n_real, neg0, mw0, self.BIG)
         big = {k: batch[k].contiguous() for k in ("video_feat", "words_id")
                if batch[k].numel() * batch[k].element_size() > self.BIG}
@@ -104,14 +71,14 @@ class HostPipeline:
         """ring-slot bytes the big tensors of `raw` need once prepared (shapes only, nothing is copied)"""
         n = raw["video_feat"].shape[0]
         if self.pairs:
-            n = _round_up(n, self.pairs)
+            n = round_up(n, self.pairs)
         tot = 0
         for k, L in (("video_feat", self.pad[0] if self.pad else None), ("words_id", self.pad[1] if self.pad else None)):
             t = raw[k]
             ext = max(t.shape[1], L) if (L is not None and t.dim() >= 2) else (t.shape[1] if t.dim() >= 2 else 1)
             nb = n * ext * int(np.prod(t.shape[2:])) * t.element_size()
             if nb > self.BIG:
-                tot += (nb + 255) // 256 * 256
+                tot += round_up(nb, 256)
         return tot
 
     __call__ = prepare
@@ -125,7 +92,7 @@ class PinnedRing:
            "uint8": torch.uint8, "bool": torch.bool, "float64": torch.float64}
 
     def __init__(self, slot_bytes, slots, pin=True):
-        self.slot_bytes = (int(slot_bytes) + 4095) // 4096 * 4096
+        self.slot_bytes = round_up(int(slot_bytes), 4096)
         self.slots = int(slots)
         self.buf = torch.empty(self.slot_bytes * self.slots, dtype=torch.uint8).share_memory_()
         self.pinned = False
@@ -163,7 +130,7 @@ class PinnedRing:
             dst = self.buf[base + off:base + off + nb].view(t.dtype).view(t.shape)
             dst.copy_(t)
             desc[k] = ("ring", int(slot) % self.slots, off, tuple(t.shape), str(t.dtype).replace("torch.", ""))
-            off += (nb + 255) // 256 * 256
+            off += round_up(nb, 256)
         return desc
 
     def get(self, desc):

@@ -413,24 +413,19 @@ class MESM(nn.Module):
         dev = video_feat.device
         is_training = kwargs["is_training"]
         auto = self._auto if self._auto is not None else self.autograph()
-        if auto.eligible(self, {"video_feat": video_feat}, kwargs):
+        train = auto.eligible(self, {"video_feat": video_feat}, kwargs)
+        evaluate = not train and auto.eligible_eval(self, {"video_feat": video_feat}, kwargs)
+        if train or evaluate:
             batch = dict(video_feat=video_feat, video_mask=video_mask, words_id=words_id, words_mask=words_mask,
                          words_weight=words_weight, num_clips=num_clips)
             batch.update({k: v for k, v in kwargs.items() if k not in ("dataset_name", "is_training", "plan")})
-            res = auto.forward(batch, kwargs["dataset_name"])
+            res = (auto.forward if train else auto.forward_eval)(batch, kwargs["dataset_name"])
             if res is not None:
                 return res
-        elif auto.eligible_eval(self, {"video_feat": video_feat}, kwargs):
-            batch = dict(video_feat=video_feat, video_mask=video_mask, words_id=words_id, words_mask=words_mask,
-                         words_weight=words_weight, num_clips=num_clips)
-            batch.update({k: v for k, v in kwargs.items() if k not in ("dataset_name", "is_training", "plan")})
-            res = auto.forward_eval(batch, kwargs["dataset_name"])
-            if res is not None:
-                return res
-            if auto.eval_neg is not None:  # the call's draw has been made: the eager forward takes it
-                kwargs = dict(kwargs, neg_index=torch.from_numpy(auto.eval_neg))
-                auto.eval_neg = None
-        elif torch.is_grad_enabled() and not auto.busy:
+        if evaluate and auto.eval_neg is not None:  # the call's draw has been made: the eager forward takes it
+            kwargs = dict(kwargs, neg_index=torch.from_numpy(auto.eval_neg))
+            auto.eval_neg = None
+        elif not (train or evaluate) and torch.is_grad_enabled() and not auto.busy:
             auto.gen += 1
         side = auto.eager_stream(dev)
         if side is not None:

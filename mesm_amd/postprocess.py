@@ -12,6 +12,7 @@ import numpy as np
 import torch
 
 from ._lib import check, lib, ptr, require_gpu, stream_ptr
+from .criterion import loss_pack
 
 
 def raw_windows(pred_logits, pred_spans, duration):
@@ -143,9 +144,8 @@ def _loss_vector(loss_dict, loss, device):
     `loss`); entries may be tensors or plain numbers"""
     names = list(loss_dict)
     vals = list(loss_dict.values())
-    pack = getattr(vals[0], "_pack", None) if vals else None
-    if pack is not None and all(getattr(v, "_pack", None) is pack for v in vals) and torch.is_tensor(loss) \
-            and pack.vec.dtype == loss.dtype and loss.device == pack.vec.device:
+    pack = loss_pack(loss_dict)
+    if pack is not None and torch.is_tensor(loss) and pack.vec.dtype == loss.dtype and loss.device == pack.vec.device:
         idx = torch.tensor([int(v._i) for v in vals], device=pack.vec.device)
         return names, torch.cat([pack.vec.detach()[idx], loss.detach().reshape(1)]).to(device)
     f64 = lambda v: (v.detach() if torch.is_tensor(v) else torch.as_tensor(float(v), dtype=torch.float64)).to(device=device, dtype=torch.float64).reshape(())

@@ -165,3 +165,73 @@ def test_prepare_batch_input_keeps_the_host_side_of_a_host_batch_bound_for_the_g
         assert "_host" not in B.prepare_batch_input(dict(out), torch.device("cuda:0"))
     finally:
         B._KEEP_HOST_SIDE = True
+
+
+def _ragged(name, groups):
+    from mesm_amd import synthetic
+    w = synthetic.WORKLOADS[name]
+    return synthetic.make_batch(w["dataset_name"], groups, w["Lv"] - 3, w["Lw"] - 2, w["v_feat_dim"], w["t_feat_dim"],
+                                w["vocab_size"] + 1, seed=3, ragged=True)
+
+
+def _pipeline(name, pairs):
+    from mesm_amd import synthetic
+    from mesm_amd.hostplan import HostSpec
+    from mesm_amd.loader import HostPipeline
+    w = synthetic.WORKLOADS[name]
+    return HostPipeline(HostSpec.from_args(synthetic.make_args(name)), pad=(w["Lv"], w["Lw"]), pairs=pairs,
+                        group_caps=(5, 9), keep_raw=False)
+
+
+@pytest.mark.parametrize("name", ["C2", "C3a"])
+@pytest.mark.parametrize("pairs", [8, 16])
+@pytest.mark.parametrize("groups", [[5, 4, 4], [9, 3, 1, 2], [2, 1, 3], [1] * 11, [6, 3]])
+def test_loader_workers_and_the_step_cache_key_a_batch_alike(name, pairs, groups):
+    """batching.shape_batch + bucket_key (what StepCache.run computes) give the key a loader worker's HostPipeline.prepare
+    ships: StepCache.run_prepared finds its graph by that key."""
+    from mesm_amd import synthetic
+    from mesm_amd.batching import bucket_key, shape_batch
+    w = synthetic.WORKLOADS[name]
+    b = _ragged(name, groups)
+    shaped = shape_batch(b, (w["Lv"], w["Lw"]), pairs)
+    assert shaped["video_mask"].shape == (-(-sum(groups) // pairs) * pairs, w["Lv"])
+    assert _pipeline(name, pairs).prepare(b)["key"] == bucket_key(shaped, (5, 9))
+
+
+@pytest.mark.parametrize("name,groups,pairs,key", [
+    ("C2", [5, 4, 4], 8, ((16, 75, 2818), (16, 16, 512), 5)),
+    ("C3a", [9, 3, 1, 2], 16, ((16, 75, 2818), (16, 32, 512), 9)),
+])
+def test_bucket_keys_are_pinned(name, groups, pairs, key):
+    """the keys of two batches written out: guards against both sides of the comparison above drifting together"""
+    from mesm_amd import synthetic
+    from mesm_amd.batching import bucket_key, shape_batch
+    w = synthetic.WORKLOADS[name]
+    b = _ragged(name, groups)
+    assert _pipeline(name, pairs).prepare(b)["key"] == key
+    assert bucket_key(shape_batch(b, (w["Lv"], w["Lw"]), pairs), (5, 9)) == key
+
+
+@pytest.mark.parametrize("extent", ["video_feat", "words_id"])
+def test_a_batch_beyond_pad_raises_and_autograph_runs_it_eagerly(extent):
+    """shape_batch raises ValueError for a clip / word extent above `pad`; AutoGraph's preamble turns that into "eager"
+    (None), and serves the same batch once `pad` holds it"""
+    import types
+    from mesm_amd import synthetic
+    from mesm_amd.autograph import AutoGraph
+    from mesm_amd.batching import shape_batch
+    w = synthetic.WORKLOADS["C3a"]
+    b = _ragged("C3a", [2, 1, 3])
+    Lv, Lw = b["video_feat"].shape[1], b["words_id"].shape[1]
+    small = (Lv - 1, Lw) if extent == "video_feat" else (Lv, Lw - 1)
+    with pytest.raises(ValueError, match="exceed pad"):
+        shape_batch(b, small, 8)
+    auto = AutoGraph.__new__(AutoGraph)
+    auto.pairs, auto.host_side = 8, 0
+    model = types.SimpleNamespace(training=True)
+    auto.pad = small
+    assert auto._prepare(model, b, w["dataset_name"], None, train=True) is None
+    auto.pad = (w["Lv"], w["Lw"])
+    shaped, host, key, gcap = auto._prepare(model, b, w["dataset_name"], None, train=True)
+    assert host is None and shaped["video_mask"].shape == (8, w["Lv"]) and shaped["_n_real"] == 6
+    assert gcap == 3 and key[2:6] == (8, (w["Lv"], w["v_feat_dim"]), (w["Lw"], w["t_feat_dim"]), 3)

@@ -36,7 +36,7 @@ for _ in range(3):
     step()
 torch.cuda.synchronize()
 auto = model._auto
-st = next(iter(auto.steps.values()))[0]
+st = next(iter(auto.train_graphs.steps.values()))[0]
 wrap(auto, "fetch", "fetch (pack + D2H + sync + unpack)")
 wrap(st.spec, "plan_arrays", "  plan_arrays")
 wrap(TargetPlan, "arrays", "  TargetPlan.arrays")
