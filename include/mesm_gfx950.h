@@ -269,6 +269,23 @@ typedef struct MesmLnArgs {
 int mesm_layernorm_fwd_group(const MesmLnArgs* list, int32_t n, void* stream);
 int mesm_layernorm_bwd_group(const MesmLnArgs* list, int32_t n, void* stream);
 
+/*
+ * The same two phases over raw input features stored as float16 (model.py:166, 201: the LayerNorm of input_vid_proj
+ * over the 2818 / 4098-d video features, the only large tensor a step moves from the host).  Every x of the list points
+ * to rows x D IEEE half values (the struct field keeps its type and carries the address); gamma, beta, y, mean, rstd, dy,
+ * dgamma, dbeta stay float.  These are entry points of their own, and MesmLnArgs keeps its layout, so that a list can
+ * never mix the two element types: twins are found among problems of one type by construction.
+ * Every lane loads the columns it loads in the float form (8-byte vectors instead of 16-byte ones) and widens in
+ * registers, and every sum runs in the same order: fwd results are bit-identical to mesm_layernorm_fwd_group over the
+ * widened x.  Covered: the forward (every width class, fused dropout, the twin launch of two problems over one x) and
+ * the parameter-gradient backward (dx == NULL; single and twin).  Raw features carry no gradient: dx, dx2, dyb, addend,
+ * accumulate_dx, relu_in, add, y2 must be zero (MESM_EINVAL otherwise).  A forward x that is not 8-byte aligned is
+ * MESM_EALIGN (the backward reads x element by element: 2-byte alignment); every problem is checked before the first
+ * launch, so a rejected list has launched nothing.
+ */
+int mesm_layernorm_fwd_group_xh(const MesmLnArgs* list, int32_t n, void* stream);
+int mesm_layernorm_bwd_group_xh(const MesmLnArgs* list, int32_t n, void* stream);
+
 /* ------------------------------------------------------------------------- */
 /*
  * Multi-head attention core: scores = scale * Q K^T -> mask(-inf) -> softmax ->

@@ -47,7 +47,7 @@ import weakref
 import torch
 
 from . import kernels as kn
-from .batching import group_bucket, shape_batch
+from .batching import feature_tag, group_bucket, shape_batch
 
 
 class AutoOutputs(dict):
@@ -269,7 +269,7 @@ class AutoGraph:
         gcap = group_bucket(batch["num_clips"] if num_clips is None else num_clips, GROUP_CAPS)
         sig = tuple(sorted(k for k, v in batch.items() if not k.startswith("_")))
         return (dataset_name, bool(model.training), n, tuple(batch["video_feat"].shape[1:]),
-                tuple(batch["words_id"].shape[1:]), gcap, "_n_real" in batch, sig), gcap
+                tuple(batch["words_id"].shape[1:]), gcap, "_n_real" in batch, sig) + feature_tag(batch), gcap
 
     def eligible(self, model, batch, kwargs):
         return (self.enabled and not self.busy and kwargs.get("is_training") is True and kwargs.get("plan") is None

@@ -192,12 +192,19 @@ class _Packer:
 _KEEP_HOST_SIDE = os.environ.get("MESM_KEEP_HOST_SIDE", "1") != "0"
 
 
-def prepare_batch_input(batched_data, device, non_blocking=False):
+def prepare_batch_input(batched_data, device, non_blocking=False, feature_dtype=None):
     """dataset/base.py:358-384 (mutates and returns `batched_data`).  One addition: a HOST batch on its way to a GPU keeps the
     host copies of its small tensors under `batched_data["_host"]` (attach_host_side: they are in hand here, and the step's
     host arithmetic needs them -- without them the unchanged `model(**batch)` call has to fetch them back behind a device
-    synchronisation, ~0.5 ms per step); a batch whose collate attached them already is left alone."""
+    synchronisation, ~0.5 ms per step); a batch whose collate attached them already is left alone.
+    feature_dtype=torch.float16 (or MESM_FEATURE_DTYPE=float16 for a loop that is not to be edited): `video_feat` is cast on
+    the HOST, before the transfer -- half the bytes of the one big tensor a step moves; the model takes it as it is."""
     device = torch.device(device)
+    fdt = feature_dtype_option(feature_dtype)
+    vf = batched_data.get("video_feat")
+    if fdt is not None and torch.is_tensor(vf) and not vf.is_cuda and vf.dtype != fdt:
+        # (before the host side is attached: a small batch's host copy has the type of what the device gets)
+        batched_data["video_feat"] = vf.to(fdt).pin_memory() if vf.is_pinned() else vf.to(fdt)
     if (_KEEP_HOST_SIDE and device.type == "cuda" and "_host" not in batched_data
             and all(not v.is_cuda for v in batched_data.values() if isinstance(v, torch.Tensor))):
         attach_host_side(batched_data)
@@ -323,4 +330,28 @@ def bucket_key(batch, group_caps=None):
     host batch keep their real rows only."""
     n = batch["video_mask"].shape[0]
     key = ((n,) + tuple(batch["video_feat"].shape[1:]), (n,) + tuple(batch["words_id"].shape[1:]))
-    return key + (group_bucket(batch["num_clips"], group_caps),) if group_caps else key
+    if group_caps:
+        key += (group_bucket(batch["num_clips"], group_caps),)
+    return key + feature_tag(batch)
+
+
+def feature_tag(batch):
+    """() for float32 video features, ("float16",) otherwise: a graph captured over one element type must never replay a
+    batch of the other (its static input would convert the features on the way in)"""
+    dt = batch["video_feat"].dtype
+    return () if dt == torch.float32 else (str(dt).replace("torch.", ""),)
+
+
+def feature_dtype_option(feature_dtype=None):
+    """the element type video features are cast to at the host boundary: the argument, else MESM_FEATURE_DTYPE (read per call),
+    else None (as they come)"""
+    if feature_dtype is None:
+        name = os.environ.get("MESM_FEATURE_DTYPE", "")
+        if not name:
+            return None
+        feature_dtype = {"float16": torch.float16, "half": torch.float16, "float32": torch.float32}.get(name)
+        if feature_dtype is None:
+            raise ValueError("MESM_FEATURE_DTYPE=%r: float32 or float16" % name)
+    if feature_dtype not in (torch.float32, torch.float16):
+        raise TypeError("feature_dtype must be torch.float32 or torch.float16, got %r" % (feature_dtype,))
+    return feature_dtype

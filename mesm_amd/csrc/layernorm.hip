@@ -4,6 +4,7 @@
 // writes dx once; dgamma/dbeta are reduced per workgroup through LDS and added
 // atomically (few adders per address: the grid is capped).
 #include <cstddef>
+#include <hip/hip_fp16.h>
 #include "common.hpp"
 
 namespace {
@@ -55,6 +56,25 @@ __device__ __forceinline__ void ld_vec(const float* __restrict__ p, float* d) {
   }
 }
 
+// x may be stored as __half (raw video features kept in float16): the same lanes load the same columns, 8 / 4 / 2
+// bytes instead of 16 / 8 / 4, and widen in registers -- exact, so every sum sees the values the float form sees
+template <int VEC>
+__device__ __forceinline__ void ld_vec(const __half* __restrict__ p, float* d) {
+  if (VEC == 4) {
+    const uint2 t = *reinterpret_cast<const uint2*>(p);
+    const float2 a = __half22float2(*reinterpret_cast<const __half2*>(&t.x));
+    const float2 b = __half22float2(*reinterpret_cast<const __half2*>(&t.y));
+    d[0] = a.x; d[1] = a.y; d[2] = b.x; d[3] = b.y;
+  } else if (VEC == 2) {
+    const float2 a = __half22float2(*reinterpret_cast<const __half2*>(p));
+    d[0] = a.x; d[1] = a.y;
+  } else {
+    d[0] = __half2float(*p);
+  }
+}
+__device__ __forceinline__ float ld_one(const float* __restrict__ p) { return *p; }
+__device__ __forceinline__ float ld_one(const __half* __restrict__ p) { return __half2float(*p); }
+
 template <int VEC>
 __device__ __forceinline__ void st_lds(float* __restrict__ p, const float* s) {  // (LDS scratch: plain stores)
   if (VEC == 4) *reinterpret_cast<float4*>(p) = make_float4(s[0], s[1], s[2], s[3]);
@@ -79,11 +99,13 @@ __device__ __forceinline__ void st_vec(float* __restrict__ p, const float* s) {
 #endif
 }
 
-// TAIL (VEC = 4 only): D is not a multiple of 4, so rows start 8- or 4-byte aligned.  The lane chunks are SHIFTED per
+// TAIL (VEC = 4 only; 1: D even, 2: any D): D is not a multiple of 4, so rows start 8- or 4-byte aligned.  The lane chunks are SHIFTED per
 // row by s = (row * D) & 3 elements so that every interior chunk is a 16-byte ALIGNED access (misaligned 16-byte accesses
 // run at about half rate here: 2400 x 2818 20.8 -> 29.7 us); the first and the last chunk of a row are partial and go
 // element by element.  The 2-wide / 1-wide paths this replaces ran 36 / 72 narrow accesses per lane and row:
 // 8192 x 4098 (TACoS) 192 us = 1.4 TB/s against 69 us at 4096 columns.
+// TAIL = 2 takes the odd widths the 1-wide path has no register class for (D > 2304): x and y chunks are aligned all the
+// same, gamma / beta go element by element.
 // A TWIN output (tw.y != NULL): the same input normalised once, written twice under two dropout masks -- the reference
 // projects the raw video features twice (model.py:166, 201: the main path and the SS-MESM copy of the batch), each through
 // its own Dropout; when the copy IS the batch the two LayerNorms read the same 27 MB.
@@ -94,9 +116,9 @@ struct LnTwin {
   LnDrop dr;
 };
 
-template <int VEC, int NCH, bool TAIL = false>
+template <int VEC, int NCH, int TAIL = 0, class XT>
 __device__ __forceinline__ void ln_fwd_body(
-    const float* __restrict__ x, const float* __restrict__ gamma,
+    const XT* __restrict__ x, const float* __restrict__ gamma,
     const float* __restrict__ beta, float* __restrict__ y, float* __restrict__ mean,
     float* __restrict__ rstd, int64_t rows, int D, float eps, LnDrop dr,
     const float* __restrict__ add, float* __restrict__ y2, int bid, int nblk, const LnTwin tw = LnTwin{}) {
@@ -107,7 +129,7 @@ __device__ __forceinline__ void ln_fwd_body(
   const uint32_t dseed = dr.seed + (dr.seed_offset ? *dr.seed_offset : 0u);
   const uint32_t dseed_b = tw.dr.seed + (tw.dr.seed_offset ? *tw.dr.seed_offset : 0u);
   for (int64_t row = wave_global; row < rows; row += nwaves) {
-    const float* xr = x + row * D;
+    const XT* xr = x + row * D;
     const int sh = TAIL ? (int)((row * D) & 3) : 0;  // chunk c of lane l starts at column (c * 64 + l) * VEC - sh
     float v[NCH][VEC];
     float s = 0.0f;
@@ -121,7 +143,7 @@ __device__ __forceinline__ void ln_fwd_body(
       } else {
 #pragma unroll
         for (int e = 0; e < VEC; ++e) {
-          v[c][e] = (TAIL && col + e >= 0 && col + e < D) ? xr[col + e] : 0.0f;
+          v[c][e] = (TAIL && col + e >= 0 && col + e < D) ? ld_one(xr + col + e) : 0.0f;
           s += v[c][e];
         }
       }
@@ -161,7 +183,13 @@ __device__ __forceinline__ void ln_fwd_body(
         }
       } else if (full) {
         float g[VEC], b[VEC], o[VEC];
-        if (TAIL) {  // (gamma + col is only 8-byte aligned when the row is shifted)
+        if (TAIL == 2) {  // (odd D: gamma + col has no alignment to speak of)
+#pragma unroll
+          for (int e = 0; e < VEC; ++e) {
+            g[e] = gamma[col + e];
+            b[e] = beta[col + e];
+          }
+        } else if (TAIL) {  // (gamma + col is only 8-byte aligned when the row is shifted)
 #pragma unroll
           for (int e = 0; e < VEC; e += 2) {
             ld_vec<2>(gamma + col + e, g + e);
@@ -245,20 +273,20 @@ __device__ __forceinline__ LnProb ln_group_pick(const LnGroup& g, int& local, in
   return *reinterpret_cast<const LnProb*>(ka + offsetof(LnGroup, p) + (size_t)gi * sizeof(LnProb));
 }
 
-template <int VEC, int NCH, bool TAIL = false>
+template <int VEC, int NCH, int TAIL, class XT>
 __global__ __launch_bounds__(LN_THREADS) void ln_fwd_kernel(
-    const float* __restrict__ x, const float* __restrict__ gamma,
+    const XT* __restrict__ x, const float* __restrict__ gamma,
     const float* __restrict__ beta, float* __restrict__ y, float* __restrict__ mean,
     float* __restrict__ rstd, int64_t rows, int D, float eps, LnDrop dr,
     const float* __restrict__ add, float* __restrict__ y2) {
   ln_fwd_body<VEC, NCH, TAIL>(x, gamma, beta, y, mean, rstd, rows, D, eps, dr, add, y2, blockIdx.x, gridDim.x);
 }
 
-template <int NCH>
+template <int NCH, class XT>
 __global__ __launch_bounds__(LN_THREADS) void ln_fwd_twin_kernel(
-    const float* __restrict__ x, const float* __restrict__ gamma, const float* __restrict__ beta, float* __restrict__ y,
+    const XT* __restrict__ x, const float* __restrict__ gamma, const float* __restrict__ beta, float* __restrict__ y,
     float* __restrict__ mean, float* __restrict__ rstd, int64_t rows, int D, float eps, LnDrop dr, const LnTwin tw) {
-  ln_fwd_body<4, NCH, true>(x, gamma, beta, y, mean, rstd, rows, D, eps, dr, nullptr, nullptr, blockIdx.x, gridDim.x, tw);
+  ln_fwd_body<4, NCH, 1>(x, gamma, beta, y, mean, rstd, rows, D, eps, dr, nullptr, nullptr, blockIdx.x, gridDim.x, tw);
 }
 
 // up to LN_GROUP_MAX independent LayerNorms (same VEC / NCH class) in ONE launch
@@ -432,8 +460,9 @@ __global__ __launch_bounds__(LNB_THREADS) void ln_bwd_group_kernel(const LnGroup
 // otherwise), meet in LDS, and wave 0 issues the one atomic per column and workgroup.
 // dy_b / dr_b (optional): the gradient of a TWIN output (LnTwin: the same x normalised once, two dropout masks) -- x is read
 // once for both.
+template <class XT>
 __global__ __launch_bounds__(256) void ln_bwd_params_kernel(
-    const float* __restrict__ dy, const float* __restrict__ x, const float* __restrict__ mean,
+    const float* __restrict__ dy, const XT* __restrict__ x, const float* __restrict__ mean,
     const float* __restrict__ rstd, float* __restrict__ dgamma, float* __restrict__ dbeta, int64_t rows,
     int D, int rows_per_block, LnDrop dr, const float* __restrict__ dy_b, LnDrop dr_b) {
   __shared__ float red[2][3][64];
@@ -453,7 +482,7 @@ __global__ __launch_bounds__(256) void ln_bwd_params_kernel(
       const int64_t rr = r + 4 * u < r1 ? r + 4 * u : r1 - 1;
       d[u] = dy[rr * D + c];
       d2[u] = dy_b ? dy_b[rr * D + c] : 0.0f;
-      xv[u] = x[rr * D + c];
+      xv[u] = ld_one(x + rr * D + c);
       mu[u] = mean[rr];
       rs[u] = rstd[rr];
     }
@@ -498,24 +527,30 @@ inline int pick_vec(int D, const void* a, const void* b, const void* c, const vo
   return vec;
 }
 
-template <int VEC, int NCH, bool TAIL = false>
-int fwd_launch(const float* x, const float* gamma, const float* beta, float* y, float* mean,
+template <int VEC, int NCH, int TAIL = 0, class XT>
+int fwd_launch(const XT* x, const float* gamma, const float* beta, float* y, float* mean,
                float* rstd, int64_t rows, int D, float eps, LnDrop dr, const float* add, float* y2,
                hipStream_t s) {
   int64_t blocks = (rows + LN_WAVES - 1) / LN_WAVES;
   if (blocks > 4096) blocks = 4096;
-  hipLaunchKernelGGL((ln_fwd_kernel<VEC, NCH, TAIL>), dim3((unsigned)blocks), dim3(LN_THREADS), 0, s, x,
+  hipLaunchKernelGGL((ln_fwd_kernel<VEC, NCH, TAIL, XT>), dim3((unsigned)blocks), dim3(LN_THREADS), 0, s, x,
                      gamma, beta, y, mean, rstd, rows, D, eps, dr, add, y2);
   return mesm_launch_status();
 }
 
 // wide rows whose length is not a multiple of 4 (2818, 4098 feature columns): 16-byte accesses with a partial last chunk
-int fwd_launch_tail(const float* x, const float* gamma, const float* beta, float* y, float* mean, float* rstd,
+template <int TAIL, class XT>
+int fwd_launch_tail(const XT* x, const float* gamma, const float* beta, float* y, float* mean, float* rstd,
                     int64_t rows, int D, float eps, LnDrop dr, const float* add, float* y2, hipStream_t s) {
   const int need = (D + 3 + 255) / 256;
-  if (need <= 8) return fwd_launch<4, 8, true>(x, gamma, beta, y, mean, rstd, rows, D, eps, dr, add, y2, s);
-  if (need <= 12) return fwd_launch<4, 12, true>(x, gamma, beta, y, mean, rstd, rows, D, eps, dr, add, y2, s);
-  if (need <= 17) return fwd_launch<4, 17, true>(x, gamma, beta, y, mean, rstd, rows, D, eps, dr, add, y2, s);
+  if (TAIL == 2) {  // (odd D above the 1-wide classes: 2305 .. 4349 columns)
+    if (need <= 12) return fwd_launch<4, 12, 2>(x, gamma, beta, y, mean, rstd, rows, D, eps, dr, add, y2, s);
+    if (need <= 17) return fwd_launch<4, 17, 2>(x, gamma, beta, y, mean, rstd, rows, D, eps, dr, add, y2, s);
+    return MESM_EINVAL;
+  }
+  if (need <= 8) return fwd_launch<4, 8, 1>(x, gamma, beta, y, mean, rstd, rows, D, eps, dr, add, y2, s);
+  if (need <= 12) return fwd_launch<4, 12, 1>(x, gamma, beta, y, mean, rstd, rows, D, eps, dr, add, y2, s);
+  if (need <= 17) return fwd_launch<4, 17, 1>(x, gamma, beta, y, mean, rstd, rows, D, eps, dr, add, y2, s);
   return MESM_EINVAL;
 }
 
@@ -555,6 +590,42 @@ int bwd_launch(const float* dy, const float* x, const float* gamma, const float*
     return MESM_EINVAL;                                            \
   } while (0)
 
+// a __half x counts as aligned for every vector width once its base is 8-byte aligned (the entry points check that):
+// the class then depends on D and on the float operands alone, i.e. it is the class of the same problem over widened x
+inline const void* ln_x_align(const float* x) { return x; }
+inline const void* ln_x_align(const __half*) { return nullptr; }
+
+template <class XT>
+int ln_fwd_any(const XT* x, const float* gamma, const float* beta, float* y, float* mean, float* rstd, int64_t rows, int D,
+               float eps, LnDrop dr, const float* add, float* y2, hipStream_t s) {
+  const void* xa = ln_x_align(x);
+  int vec = pick_vec(D, xa, y, gamma, beta);
+  if (add && vec > pick_vec(D, add, y2, nullptr, nullptr)) vec = pick_vec(D, add, y2, nullptr, nullptr);
+  static const bool no_tail = getenv("MESM_LN_NO_TAIL") != nullptr;  // A/B: the narrow-vector paths
+  if (vec < 4 && !no_tail && D + 3 <= 17 * 256 && pick_vec(4, xa, y, gamma, beta) == 4 &&
+      (!add || pick_vec(4, add, y2, nullptr, nullptr) == 4)) {
+    if (D % 4 == 2 && D >= 1024) return fwd_launch_tail<1>(x, gamma, beta, y, mean, rstd, rows, D, eps, dr, add, y2, s);
+    if (D % 2 == 1 && D > 36 * 64) return fwd_launch_tail<2>(x, gamma, beta, y, mean, rstd, rows, D, eps, dr, add, y2, s);
+  }
+  if (vec == 4) LN_DISPATCH(fwd_launch, 4, x, gamma, beta, y, mean, rstd, rows, D, eps, dr, add, y2, s);
+  if (vec == 2) LN_DISPATCH(fwd_launch, 2, x, gamma, beta, y, mean, rstd, rows, D, eps, dr, add, y2, s);
+  LN_DISPATCH(fwd_launch, 1, x, gamma, beta, y, mean, rstd, rows, D, eps, dr, add, y2, s);
+}
+
+// parameter gradients only: about 1024 workgroups, of 32 rows or more; dy_b / dr_b: the twin's gradient (or NULL)
+template <class XT>
+int ln_bwd_params_launch(const float* dy, const XT* x, const float* mean, const float* rstd, float* dgamma, float* dbeta,
+                         int64_t rows, int D, LnDrop dr, const float* dy_b, LnDrop dr_b, hipStream_t s) {
+  const int cb = (D + 63) / 64;
+  int rb = (int)((1024 + cb - 1) / cb);
+  if ((int64_t)rb * 32 > rows) rb = (int)((rows + 31) / 32);
+  const int rpb = (int)((rows + rb - 1) / rb);
+  rb = (int)((rows + rpb - 1) / rpb);
+  hipLaunchKernelGGL(ln_bwd_params_kernel<XT>, dim3(cb, rb), dim3(256), 0, s, dy, x, mean, rstd, dgamma, dbeta, rows, D, rpb,
+                     dr, dy_b, dr_b);
+  return mesm_launch_status();
+}
+
 }  // namespace
 
 extern "C" int mesm_layernorm_fwd2(const float* x, const float* gamma, const float* beta,
@@ -565,17 +636,8 @@ extern "C" int mesm_layernorm_fwd2(const float* x, const float* gamma, const flo
   if (drop_p < 0.f || drop_p >= 1.f) return MESM_EINVAL;
   if ((add == nullptr) != (y2 == nullptr)) return MESM_EINVAL;
   if (rows == 0) return MESM_OK;
-  hipStream_t s = (hipStream_t)stream;
-  const LnDrop dr = make_drop(drop_p, drop_seed, seed_offset);
-  int vec = pick_vec(D, x, y, gamma, beta);
-  if (add && vec > pick_vec(D, add, y2, nullptr, nullptr)) vec = pick_vec(D, add, y2, nullptr, nullptr);
-  static const bool no_tail = getenv("MESM_LN_NO_TAIL") != nullptr;  // A/B: the narrow-vector paths
-  if (vec < 4 && !no_tail && D % 4 == 2 && D >= 1024 && D + 3 <= 17 * 256 && pick_vec(4, x, y, gamma, beta) == 4 &&
-      (!add || pick_vec(4, add, y2, nullptr, nullptr) == 4))
-    return fwd_launch_tail(x, gamma, beta, y, mean, rstd, rows, D, eps, dr, add, y2, s);
-  if (vec == 4) LN_DISPATCH(fwd_launch, 4, x, gamma, beta, y, mean, rstd, rows, D, eps, dr, add, y2, s);
-  if (vec == 2) LN_DISPATCH(fwd_launch, 2, x, gamma, beta, y, mean, rstd, rows, D, eps, dr, add, y2, s);
-  LN_DISPATCH(fwd_launch, 1, x, gamma, beta, y, mean, rstd, rows, D, eps, dr, add, y2, s);
+  return ln_fwd_any(x, gamma, beta, y, mean, rstd, rows, D, eps, make_drop(drop_p, drop_seed, seed_offset), add, y2,
+                    (hipStream_t)stream);
 }
 
 extern "C" int mesm_layernorm_fwd(const float* x, const float* gamma, const float* beta,
@@ -602,14 +664,7 @@ extern "C" int mesm_layernorm_bwd3(const float* dy, const float* x, const float*
   const LnDrop dr = make_drop(drop_p, drop_seed, seed_offset);
   if (!dx) {
     if (accumulate_dx || dyb || addend) return MESM_EINVAL;
-    const int cb = (D + 63) / 64;
-    int rb = (int)((1024 + cb - 1) / cb);  // about 1024 workgroups, of 32 rows or more
-    if ((int64_t)rb * 32 > rows) rb = (int)((rows + 31) / 32);
-    const int rpb = (int)((rows + rb - 1) / rb);
-    rb = (int)((rows + rpb - 1) / rpb);
-    hipLaunchKernelGGL(ln_bwd_params_kernel, dim3(cb, rb), dim3(256), 0, s, dy, x, mean, rstd, dgamma,
-                       dbeta, rows, D, rpb, dr, (const float*)nullptr, LnDrop{});
-    return mesm_launch_status();
+    return ln_bwd_params_launch(dy, x, mean, rstd, dgamma, dbeta, rows, D, dr, (const float*)nullptr, LnDrop{}, s);
   }
   int vec = pick_vec(D, x, dy, dx, gamma);
   const int vec2 = pick_vec(D, dyb, addend, dx2, nullptr);
@@ -660,13 +715,14 @@ int ln_group_class(const MesmLnArgs& a, bool bwd) {
 
 // twins: two LayerNorm problems of one phase over the SAME x / gamma / beta with different dropout masks (the raw video
 // features projected for the main path and for the SS-MESM copy of the batch when the copy is the batch itself)
-bool ln_fwd_twins(const MesmLnArgs& a, const MesmLnArgs& b) {
+bool ln_fwd_twins(const MesmLnArgs& a, const MesmLnArgs& b, bool x_half = false) {
   return a.x == b.x && a.gamma == b.gamma && a.beta == b.beta && a.rows == b.rows && a.D == b.D && a.eps == b.eps && !a.add &&
          !b.add && !a.y2 && !b.y2 && a.y != b.y && a.D % 4 == 2 && a.D >= 1024 && a.D + 3 <= 17 * 256 &&
-         pick_vec(4, a.x, a.y, a.gamma, a.beta) == 4 && pick_vec(4, b.y, nullptr, nullptr, nullptr) == 4;
+         pick_vec(4, x_half ? nullptr : a.x, a.y, a.gamma, a.beta) == 4 && pick_vec(4, b.y, nullptr, nullptr, nullptr) == 4;
 }
 
-int ln_fwd_twin_launch(const MesmLnArgs& a, const MesmLnArgs& b, hipStream_t s) {
+template <class XT>
+int ln_fwd_twin_launch(const XT* x, const MesmLnArgs& a, const MesmLnArgs& b, hipStream_t s) {
   const LnDrop dr = make_drop(a.drop_p, a.drop_seed, a.seed_offset);
   LnTwin tw;
   tw.y = b.y; tw.mean = b.mean; tw.rstd = b.rstd;
@@ -675,13 +731,13 @@ int ln_fwd_twin_launch(const MesmLnArgs& a, const MesmLnArgs& b, hipStream_t s) 
   if (blocks > 4096) blocks = 4096;
   const int need = (a.D + 3 + 255) / 256;
   if (need <= 8)
-    hipLaunchKernelGGL(ln_fwd_twin_kernel<8>, dim3((unsigned)blocks), dim3(LN_THREADS), 0, s, a.x, a.gamma, a.beta, a.y, a.mean,
-                       a.rstd, a.rows, a.D, a.eps, dr, tw);
+    hipLaunchKernelGGL((ln_fwd_twin_kernel<8, XT>), dim3((unsigned)blocks), dim3(LN_THREADS), 0, s, x, a.gamma, a.beta, a.y,
+                       a.mean, a.rstd, a.rows, a.D, a.eps, dr, tw);
   else if (need <= 12)
-    hipLaunchKernelGGL(ln_fwd_twin_kernel<12>, dim3((unsigned)blocks), dim3(LN_THREADS), 0, s, a.x, a.gamma, a.beta, a.y,
+    hipLaunchKernelGGL((ln_fwd_twin_kernel<12, XT>), dim3((unsigned)blocks), dim3(LN_THREADS), 0, s, x, a.gamma, a.beta, a.y,
                        a.mean, a.rstd, a.rows, a.D, a.eps, dr, tw);
   else
-    hipLaunchKernelGGL(ln_fwd_twin_kernel<17>, dim3((unsigned)blocks), dim3(LN_THREADS), 0, s, a.x, a.gamma, a.beta, a.y,
+    hipLaunchKernelGGL((ln_fwd_twin_kernel<17, XT>), dim3((unsigned)blocks), dim3(LN_THREADS), 0, s, x, a.gamma, a.beta, a.y,
                        a.mean, a.rstd, a.rows, a.D, a.eps, dr, tw);
   return mesm_launch_status();
 }
@@ -691,16 +747,11 @@ bool ln_bwd_param_twins(const MesmLnArgs& a, const MesmLnArgs& b) {
          a.dy != b.dy && !a.dyb && !b.dyb && !a.addend && !b.addend && !a.dx2 && !b.dx2 && a.D > 512;
 }
 
-int ln_bwd_param_twin_launch(const MesmLnArgs& a, const MesmLnArgs& b, hipStream_t s) {
-  const int cb = (a.D + 63) / 64;
-  int rb = (int)((1024 + cb - 1) / cb);  // (as mesm_layernorm_bwd3: about 1024 workgroups, of 32 rows or more)
-  if ((int64_t)rb * 32 > a.rows) rb = (int)((a.rows + 31) / 32);
-  const int rpb = (int)((a.rows + rb - 1) / rb);
-  rb = (int)((a.rows + rpb - 1) / rpb);
-  hipLaunchKernelGGL(ln_bwd_params_kernel, dim3(cb, rb), dim3(256), 0, s, a.dy, a.x, a.mean, a.rstd, a.dgamma, a.dbeta, a.rows,
-                     a.D, rpb, make_drop(a.drop_p, a.drop_seed, a.seed_offset), b.dy,
-                     make_drop(b.drop_p, b.drop_seed, b.seed_offset));
-  return mesm_launch_status();
+template <class XT>
+int ln_bwd_param_twin_launch(const XT* x, const MesmLnArgs& a, const MesmLnArgs& b, hipStream_t s) {
+  return ln_bwd_params_launch(a.dy, x, a.mean, a.rstd, a.dgamma, a.dbeta, a.rows, a.D,
+                              make_drop(a.drop_p, a.drop_seed, a.seed_offset), b.dy,
+                              make_drop(b.drop_p, b.drop_seed, b.seed_offset), s);
 }
 
 LnProb ln_prob(const MesmLnArgs& a) {
@@ -749,7 +800,7 @@ extern "C" int mesm_layernorm_fwd_group(const MesmLnArgs* list, int32_t n, void*
         ++j;
       if (j < n) {
         done[j] = true;
-        rc = ln_fwd_twin_launch(a, list[j], s);
+        rc = ln_fwd_twin_launch(a.x, a, list[j], s);
         continue;
       }
     }
@@ -803,7 +854,7 @@ extern "C" int mesm_layernorm_bwd_group(const MesmLnArgs* list, int32_t n, void*
         ++j;
       if (j < n) {
         done[j] = true;
-        rc = ln_bwd_param_twin_launch(a, list[j], s);
+        rc = ln_bwd_param_twin_launch(a.x, a, list[j], s);
         continue;
       }
     }
@@ -824,5 +875,76 @@ extern "C" int mesm_layernorm_bwd_group(const MesmLnArgs* list, int32_t n, void*
     }
   }
   for (int c = 0; c < 2 && rc == MESM_OK; ++c) flush(c);
+  return rc;
+}
+
+// ------------------------------------------------------------------------------------------------
+// The same phases over raw features stored as float16: every x of the list is a __half array (the struct's x field carries
+// the address), every other operand float.  Only what reads raw features exists in this form -- the forward (plain, fused
+// dropout, twin) and the parameter-gradient backward (single, twin); the rest is refused, never misread.
+namespace {
+
+int ln_xh_check(const MesmLnArgs& a, bool bwd) {
+  if (!a.x || a.rows < 0 || a.D <= 0 || a.drop_p < 0.f || a.drop_p >= 1.f) return MESM_EINVAL;
+  if (a.add || a.y2 || a.dx || a.dx2 || a.dyb || a.addend || a.accumulate_dx || a.relu_in) return MESM_EINVAL;
+  if (bwd) {
+    if (!a.dy || !a.mean || !a.rstd || !a.dgamma || !a.dbeta) return MESM_EINVAL;
+    return ((uintptr_t)a.x % 2) ? MESM_EALIGN : MESM_OK;  // (read element by element)
+  }
+  if (!a.gamma || !a.beta || !a.y || !a.mean || !a.rstd) return MESM_EINVAL;
+  return ((uintptr_t)a.x % 8) ? MESM_EALIGN : MESM_OK;
+}
+
+}  // namespace
+
+extern "C" int mesm_layernorm_fwd_group_xh(const MesmLnArgs* list, int32_t n, void* stream) {
+  if (!list || n <= 0 || n > 64) return MESM_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  for (int i = 0; i < n; ++i) {  // (every problem is checked before the first launch: an EALIGN caller retries the phase)
+    const int rc = ln_xh_check(list[i], false);
+    if (rc != MESM_OK) return rc;
+  }
+  bool done[64] = {};
+  int rc = MESM_OK;
+  for (int i = 0; i < n && rc == MESM_OK; ++i) {
+    const MesmLnArgs& a = list[i];
+    if (done[i] || a.rows == 0) continue;
+    const __half* x = reinterpret_cast<const __half*>(a.x);
+    int j = i + 1;
+    while (j < n && (done[j] || !ln_fwd_twins(a, list[j], true))) ++j;
+    if (j < n) {
+      done[j] = true;
+      rc = ln_fwd_twin_launch(x, a, list[j], s);
+      continue;
+    }
+    rc = ln_fwd_any(x, a.gamma, a.beta, a.y, a.mean, a.rstd, a.rows, a.D, a.eps, make_drop(a.drop_p, a.drop_seed, a.seed_offset),
+                    (const float*)nullptr, (float*)nullptr, s);
+  }
+  return rc;
+}
+
+extern "C" int mesm_layernorm_bwd_group_xh(const MesmLnArgs* list, int32_t n, void* stream) {
+  if (!list || n <= 0 || n > 64) return MESM_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  for (int i = 0; i < n; ++i) {
+    const int rc = ln_xh_check(list[i], true);
+    if (rc != MESM_OK) return rc;
+  }
+  bool done[64] = {};
+  int rc = MESM_OK;
+  for (int i = 0; i < n && rc == MESM_OK; ++i) {
+    const MesmLnArgs& a = list[i];
+    if (done[i] || a.rows == 0) continue;
+    const __half* x = reinterpret_cast<const __half*>(a.x);
+    int j = i + 1;
+    while (j < n && (done[j] || !ln_bwd_param_twins(a, list[j]))) ++j;
+    if (j < n) {
+      done[j] = true;
+      rc = ln_bwd_param_twin_launch(x, a, list[j], s);
+      continue;
+    }
+    rc = ln_bwd_params_launch(a.dy, x, a.mean, a.rstd, a.dgamma, a.dbeta, a.rows, a.D,
+                              make_drop(a.drop_p, a.drop_seed, a.seed_offset), (const float*)nullptr, LnDrop{}, s);
+  }
   return rc;
 }

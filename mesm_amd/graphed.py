@@ -304,6 +304,9 @@ class GraphedStep:
             v = batch.get(k)
             if k == "num_clips" or k.startswith("_"):
                 continue
+            if k == "video_feat" and torch.is_tensor(v) and v.dtype != cur.dtype:
+                # (copy_ would convert on the way into the static input: a float16 batch wants a graph of its own)
+                raise ValueError("GraphedStep.load_batch: video_feat changed dtype %s -> %s" % (cur.dtype, v.dtype))
             if torch.is_tensor(cur) and torch.is_tensor(v) and cur.shape != v.shape:
                 if k in ("video_feat", "words_id") and cur.shape[1:] == v.shape[1:] and v.shape[0] <= cur.shape[0] \
                         and self._n_real is not None:
@@ -406,6 +409,8 @@ class GraphedStep:
         big = prep["big"]
         for k, v in big.items():
             cur = self.batch[k]
+            if v.dtype != cur.dtype:
+                raise ValueError("GraphedStep.load_prepared: %s changed dtype %s -> %s" % (k, cur.dtype, v.dtype))
             # fewer rows than the static input only where the step reads the real pair count from the device (like
             # load_batch: without it the stale rows of the previous batch would take part in the step)
             if cur.shape[1:] != v.shape[1:] or v.shape[0] > cur.shape[0] or (v.shape[0] < cur.shape[0] and self._n_real is None):

@@ -1,7 +1,8 @@
 """Tensor-level wrappers over the C-ABI (no autograd here; see ops.py).
 
 Every function launches on torch's current HIP stream and returns immediately.
-Tensors must live on the GPU, be fp32 and (unless stated) contiguous.
+Tensors must live on the GPU, be fp32 and (unless stated) contiguous.  The one exception: the x of the LayerNorm
+wrappers may be float16 (raw video features, FEATURE_DTYPES).
 """
 import ctypes
 import os
@@ -18,6 +19,22 @@ __all__ = [
     "query_sine_fwd", "query_sine_bwd", "dropout", "act_bias_bwd",
     "ACT_NONE", "ACT_RELU", "ACT_PRELU",
 ]
+
+
+# what raw input features may be stored as (model.forward's video_feat, the x of layernorm_fwd / layernorm_bwd)
+FEATURE_DTYPES = (torch.float32, torch.float16)
+MESM_EALIGN = -2
+
+
+def _ln_dtypes(x, **f32):
+    """TypeError before any launch: among floating tensors the LayerNorm kernels read float32, or float16 for x only (a
+    tensor of another type would be misread through its address)."""
+    if x.dtype not in FEATURE_DTYPES:
+        raise TypeError("LayerNorm x must be float32 or float16 (mesm_amd.FEATURE_DTYPES), got %s" % x.dtype)
+    for name, t in f32.items():
+        if t is not None and t.dtype != torch.float32:
+            raise TypeError("LayerNorm %s must be float32 (only x may also be float16), got %s" % (name, t.dtype))
+    return x.dtype == torch.float16
 
 
 # Device scalar (uint32 stored in an int32 tensor) added to every dropout seed at run time;
@@ -367,7 +384,9 @@ class _Phase:
     """Launches queued by kind; `flush` issues every kind through its grouped entry point."""
     KINDS = (("gemm", GemmArgs, "mesm_gemm_group", "mesm_gemm_f32"),
              ("ln_fwd", LnArgs, "mesm_layernorm_fwd_group", None),
+             ("ln_fwd_xh", LnArgs, "mesm_layernorm_fwd_group_xh", None),  # float16 x: lists of their own
              ("ln_bwd", LnArgs, "mesm_layernorm_bwd_group", None),
+             ("ln_bwd_xh", LnArgs, "mesm_layernorm_bwd_group_xh", None),
              ("attn_fwd", AttnArgs, "mesm_attn_fwd_group", "mesm_attn_fwd"),
              ("attn_bwd", AttnArgs, "mesm_attn_bwd_group", "mesm_attn_bwd"),
              ("glue", _lib.GlueArgs, "mesm_glue_group", None))
@@ -462,17 +481,22 @@ gemm_group = phase  # the older name: a phase that only holds GEMMs
 def layernorm_fwd(x, gamma, beta, eps=1e-5, drop=(0.0, 0), add=None, out=None):
     """y = dropout(LN(x)) (drop = (p, seed); p = 0: plain LayerNorm), mean, rstd.
     add (same shape as x): also return y + add as a fourth value (one extra store stream).
-    out: where y is written (a contiguous tensor of x's size, e.g. a slot of a stacked output)."""
+    out: where y is written (a contiguous tensor of x's size, e.g. a slot of a stacked output).
+    x may be float16 (raw features): y, mean and rstd are float32 all the same, bit for bit what x.float() gives; no
+    `add` in that form."""
     require_gpu(x, gamma, beta)
+    xh = _ln_dtypes(x, gamma=gamma, beta=beta, add=add, out=out)
+    if xh and add is not None:
+        raise TypeError("layernorm_fwd: a float16 x takes no `add` (float32 only)")
     D = x.shape[-1]
     x2 = x.reshape(-1, D)
     assert x2.is_contiguous()
     rows = x2.shape[0]
     if out is not None:
-        assert out.is_contiguous() and out.numel() == x2.numel() and out.dtype == x2.dtype and out.device == x2.device
+        assert out.is_contiguous() and out.numel() == x2.numel() and out.dtype == torch.float32 and out.device == x2.device
         y = out.view(rows, D)
     else:
-        y = torch.empty_like(x2)
+        y = torch.empty(x2.shape, device=x2.device, dtype=torch.float32)
     mean = torch.empty(rows, device=x.device, dtype=torch.float32)
     rstd = torch.empty(rows, device=x.device, dtype=torch.float32)
     _check_drop_index(x2.numel(), float(drop[0]))
@@ -480,7 +504,9 @@ def layernorm_fwd(x, gamma, beta, eps=1e-5, drop=(0.0, 0), add=None, out=None):
     if add is not None:
         assert add.is_contiguous() and add.numel() == x2.numel()
         y2 = torch.empty_like(x2)
-    if _phase is not None:
+    if xh and _phase is not None and x2.data_ptr() % 8:
+        x2 = x2.clone()  # (a queued launch cannot be retried: what MESM_EALIGN would say is checked here)
+    if _phase is not None or xh:
         a = LnArgs()
         a.x, a.gamma, a.beta, a.y, a.mean, a.rstd = (x2.data_ptr(), gamma.data_ptr(), beta.data_ptr(), y.data_ptr(),
                                                      mean.data_ptr(), rstd.data_ptr())
@@ -488,7 +514,15 @@ def layernorm_fwd(x, gamma, beta, eps=1e-5, drop=(0.0, 0), add=None, out=None):
         a.drop_p, a.drop_seed, a.seed_offset = float(drop[0]), int(drop[1]) & 0xFFFFFFFF, _seed_off_ptr()
         if add is not None:
             a.add, a.y2 = add.data_ptr(), y2.data_ptr()
-        _phase.add("ln_fwd", a, (x2, gamma, beta, y, mean, rstd, add, y2))
+        if xh and _phase is None:
+            rc = lib().mesm_layernorm_fwd_group_xh(ctypes.byref(a), 1, stream_ptr())
+            if rc == MESM_EALIGN:  # a view that starts off an 8-byte boundary: nothing was launched; a fresh copy is aligned
+                x2 = x2.clone()
+                a.x = x2.data_ptr()
+                rc = lib().mesm_layernorm_fwd_group_xh(ctypes.byref(a), 1, stream_ptr())
+            check(rc, "mesm_layernorm_fwd_group_xh")
+            return y.view(x.shape), mean, rstd
+        _phase.add("ln_fwd_xh" if xh else "ln_fwd", a, (x2, gamma, beta, y, mean, rstd, add, y2))
         if add is not None:
             return y.view(x.shape), mean, rstd, y2.view(x.shape)
         return y.view(x.shape), mean, rstd
@@ -509,12 +543,16 @@ def layernorm_bwd(dy, x, gamma, mean, rstd, dgamma, dbeta, dx=None, accumulate_d
     another route (added to dx on store)."""
     dp, dseed = float(drop[0]), int(drop[1]) & 0xFFFFFFFF
     require_gpu(dy, x, gamma)
+    xh = _ln_dtypes(x, dy=dy, gamma=gamma, mean=mean, rstd=rstd, dgamma=dgamma, dbeta=dbeta, dx=dx, dyb=dyb, addend=addend)
+    if xh and (need_dx or drop2 is not None or dyb is not None or addend is not None or relu_in):
+        raise TypeError("layernorm_bwd: a float16 x is raw input features and carries no gradient -- need_dx=False only "
+                        "(dx, drop2, dyb, addend, relu_in want a float32 x)")
     D = x.shape[-1]
     x2 = x.reshape(-1, D)
     dy2 = dy.reshape(-1, D)
     assert x2.is_contiguous() and dy2.is_contiguous()
     assert not relu_in or (need_dx and D <= 512)
-    if _phase is not None and not need_dx and drop2 is None and dyb is None and addend is None:
+    if (_phase is not None or xh) and not need_dx and drop2 is None and dyb is None and addend is None:
         # parameter gradients only: a small problem (the 512-d word / sentence inputs) rides in the phase's grouped launch,
         # two wide ones over the same x (the raw video features' twin LayerNorms) share one pass over x
         a = LnArgs()
@@ -522,7 +560,10 @@ def layernorm_bwd(dy, x, gamma, mean, rstd, dgamma, dbeta, dx=None, accumulate_d
         a.dgamma, a.dbeta = dgamma.data_ptr(), dbeta.data_ptr()
         a.rows, a.D = x2.shape[0], D
         a.drop_p, a.drop_seed, a.seed_offset = dp, dseed, _seed_off_ptr()
-        _phase.add("ln_bwd", a, (dy2, x2, gamma, mean, rstd, dgamma, dbeta))
+        if _phase is None:
+            check(lib().mesm_layernorm_bwd_group_xh(ctypes.byref(a), 1, stream_ptr()), "mesm_layernorm_bwd_group_xh")
+            return None
+        _phase.add("ln_bwd_xh" if xh else "ln_bwd", a, (dy2, x2, gamma, mean, rstd, dgamma, dbeta))
         return None
     if (_phase is not None or relu_in) and need_dx:
         for t_ in (dyb, addend):

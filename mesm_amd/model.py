@@ -410,6 +410,12 @@ class MESM(nn.Module):
         return self._auto.configure(enabled, pad, pairs, max_graphs, eval)
 
     def forward(self, video_feat, video_mask, words_id, words_mask, words_weight, num_clips, **kwargs):
+        # the kernels read addresses: a feature tensor of another type would be misread, not converted
+        if video_feat.dtype not in kn.FEATURE_DTYPES:
+            raise TypeError("video_feat must be float32 or float16 (mesm_amd.FEATURE_DTYPES), got %s" % video_feat.dtype)
+        if words_id.dim() == 3 and words_id.dtype != torch.float32:
+            raise TypeError("pre-extracted word features (3-D words_id) must be float32 (float16 is supported for "
+                            "video_feat only), got %s" % words_id.dtype)
         dev = video_feat.device
         is_training = kwargs["is_training"]
         auto = self._auto if self._auto is not None else self.autograph()
@@ -491,6 +497,8 @@ class MESM(nn.Module):
             chains = [proj_chain(self.input_vid_proj, video_feat), proj_chain(self.input_txt_proj, words)]
             if self.rec_ss:
                 if plan.vid_src is not None and not plan.vid_identity:
+                    # (the mask is bool: the product keeps video_feat's type -- float16 features stay float16, and x * 0/1
+                    # is exact in either)
                     bvid = video_feat.reshape(N * Lv, -1)[plan.vid_src] * plan.vid_mask.unsqueeze(-1)
                     bvid_pad = plan.vid_pad
                 elif plan.vid_src is not None:

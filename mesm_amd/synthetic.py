@@ -59,8 +59,9 @@ def make_args(workload=None, **overrides):
 
 
 def make_batch(dataset_name, groups, Lv, Lw, Dv, Dt, num_classes, seed=0, ragged=False,
-               duration=150.0):
-    """Batch dict on the CPU.  `groups` = queries per video group (sum = N pairs)."""
+               duration=150.0, feature_dtype=None):
+    """Batch dict on the CPU.  `groups` = queries per video group (sum = N pairs).  feature_dtype=torch.float16: the same
+    seeded draw with `video_feat` cast (features as an extractor pipeline stores them)."""
     g = torch.Generator().manual_seed(seed)
     N = sum(groups)
     qvh = dataset_name == "qvhighlights"
@@ -82,6 +83,8 @@ def make_batch(dataset_name, groups, Lv, Lw, Dv, Dt, num_classes, seed=0, ragged
             start += gs
     video_mask = torch.arange(Lv)[None, :] < torch.tensor(vlen)[:, None]
     video_feat = video_feat * video_mask[..., None]
+    if feature_dtype is not None:
+        video_feat = video_feat.to(feature_dtype)
     # words
     wlen = [min(Lw, 4 + ((5 * i) % (Lw - 3))) for i in range(N)]
     words_mask = torch.arange(Lw)[None, :] < torch.tensor(wlen)[:, None]
@@ -136,11 +139,11 @@ def make_batch(dataset_name, groups, Lv, Lw, Dv, Dt, num_classes, seed=0, ragged
     return batch
 
 
-def workload_batch(name, seed=0, ragged=False):
+def workload_batch(name, seed=0, ragged=False, feature_dtype=None):
     w = WORKLOADS[name]
     ncls = w["vocab_size"] + 1
     return make_batch(w["dataset_name"], w["groups"], w["Lv"], w["Lw"], w["v_feat_dim"],
-                      w["t_feat_dim"], ncls, seed=seed, ragged=ragged)
+                      w["t_feat_dim"], ncls, seed=seed, ragged=ragged, feature_dtype=feature_dtype)
 
 
 def host_draws(batch, seed=0):

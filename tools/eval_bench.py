@@ -12,7 +12,9 @@ three forms:
 Every form runs the stream twice (the first pass captures the graphs of its buckets) and times the second.  Prints one
 JSON line.  `--only FORM --passes K` runs one form K times without the report (for a rocprofv3 run of its own).
 
-    python tools/eval_bench.py [--only replayed_rows --passes 2]
+    python tools/eval_bench.py [--only replayed_rows --passes 2] [--feature-dtype float16]
+
+--feature-dtype float16: the stream's video features are stored as float16 (mesm_amd.FEATURE_DTYPES); the report says so.
 """
 import argparse
 import json
@@ -30,7 +32,7 @@ import torch  # noqa: E402
 FORMS = ("eager", "replayed", "replayed_rows")
 
 
-def stream(wl, nb=36, videos=12, seed=5):
+def stream(wl, nb=36, videos=12, seed=5, feature_dtype=None):
     from mesm_amd import synthetic
     rng = random.Random(seed)
     sizes, probs = list(range(1, 10)), [0.18, 0.22, 0.20, 0.15, 0.10, 0.07, 0.04, 0.025, 0.015]
@@ -39,7 +41,7 @@ def stream(wl, nb=36, videos=12, seed=5):
     for i in range(nb):
         groups = [rng.choices(sizes, probs)[0] for _ in range(videos)]
         b = synthetic.make_batch(wl["dataset_name"], groups, wl["Lv"], wl["Lw"], wl["v_feat_dim"], wl["t_feat_dim"],
-                                 wl["vocab_size"] + 1, seed=2000 + i, ragged=True)
+                                 wl["vocab_size"] + 1, seed=2000 + i, ragged=True, feature_dtype=feature_dtype)
         b = synthetic.to_device(b, dev)
         n = sum(groups)
         b["qid"] = list(range(qid, qid + n))
@@ -122,15 +124,16 @@ def main():
     ap.add_argument("--only", choices=FORMS)
     ap.add_argument("--passes", type=int, default=2)
     ap.add_argument("--batches", type=int, default=36)
+    ap.add_argument("--feature-dtype", choices=("float32", "float16"), default="float32")
     a = ap.parse_args()
     from mesm_amd import build_criterion, build_model, synthetic
     wl = synthetic.WORKLOADS["C3a"]
     args = synthetic.make_args("C3a", device="cuda:0")
     torch.manual_seed(0)
-    batches = stream(wl, nb=a.batches)
+    batches = stream(wl, nb=a.batches, feature_dtype=getattr(torch, a.feature_dtype))
     queries = sum(b["video_feat"].shape[0] for b in batches)
     opt = argparse.Namespace(dataset_name=args.dataset_name, clip_len=2, max_ts_val=150, sort_results=True)
-    report = {"workload": "C3a", "batches": len(batches), "videos_per_batch": 12, "queries": queries,
+    report = {"workload": "C3a", "feature_dtype": a.feature_dtype, "batches": len(batches), "videos_per_batch": 12, "queries": queries,
               "pad": [75, 32], "pairs": 8, "forms": {}}
     for form in ([a.only] if a.only else FORMS):
         torch.manual_seed(1)
