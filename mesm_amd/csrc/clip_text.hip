@@ -143,7 +143,13 @@ __global__ __launch_bounds__(256) void gemm_f16_kernel(const AT* __restrict__ A,
     if (row >= M) continue;
     float v = r16(acc[r] + bv);
     if (gelu) {
-      const float t = r16(1.702f * v);
+      // the eager op rounds the product to fp32 and that to fp16.  Left to itself the compiler folds (h16)(1.702f * v)
+      // into one v_fma_mixlo_f16, which rounds the exact product once: another t wherever the fp32 product is an fp16
+      // tie (v = -1.46484375: 1276.5 * 2^-9), one fp16 step of the sigmoid's argument.  The empty asm keeps the fp32
+      // product in a register, so the two roundings stay two.
+      float p = 1.702f * v;
+      asm volatile("" : "+v"(p));
+      const float t = r16(p);
       const float s = r16(1.0f / (1.0f + __expf(-t)));
       v = r16(v * s);
     }
