@@ -898,7 +898,28 @@ int mesm_embed_rows(const int64_t* ids, const float* table, float* out, int64_t 
  *                       p -= lr/(1-b1^t) * m / (sqrt(v)/sqrt(1-b2^t) + eps)
  *                     active4 (n/4 bytes, optional): groups of 4 elements with 0 are skipped (tensors
  *                     whose gradient is None this step: no decay, no state update).
+ *   mesm_adamw_step_groups  the same update with PER-GROUP hyperparameters (torch's param_groups) and partial
+ *                     coverage.  tag4 (n/4 bytes, required) takes the place of active4: 0 skips a group of 4
+ *                     elements (a tensor no parameter group covers, or one without a gradient this step),
+ *                     k + 1 updates it with groups[k].  The flat layout pads every tensor to a multiple of
+ *                     4 elements, so a tag byte never straddles two tensors.  groups (n_groups entries,
+ *                     1..MESM_ADAM_MAX_GROUPS) lives in DEVICE memory like lr / step of mesm_adamw_step: a
+ *                     captured launch picks up every later edit of lr, betas, eps and weight_decay.  Group k
+ *                     uses t = *step - step0 (step0 = the step count when the group joined: its bias
+ *                     correction starts at t = 1, like torch's per-parameter step); a group with t < 1 is
+ *                     skipped.  lr == 0 still updates m and v and leaves p bit-unchanged.  coef and norm_out
+ *                     are those of mesm_adamw_step: the norm is that of the WHOLE g, covered or not.  With
+ *                     one group over every element the results are mesm_adamw_step's bit for bit.
+ *                     MESM_EINVAL: a null p/g/m/v/tag4/groups/step, n <= 0, n % 4, n_groups outside
+ *                     1..64, max_norm > 0 without partials or np outside 1..1024.  MESM_EALIGN: p/g/m/v off
+ *                     a 16-byte boundary (groups: 4-byte).  All checked before the launch.
  */
+#define MESM_ADAM_MAX_GROUPS 64
+typedef struct MesmAdamGroup { /* 32 bytes, lives in DEVICE memory */
+  float lr, beta1, beta2, eps, weight_decay;
+  int32_t step0; /* global step count when the group joined: t = *step - step0 */
+  int32_t pad[2];
+} MesmAdamGroup;
 int mesm_grad_sumsq(const float* g, int64_t n, float* partials, int32_t* np_out, int32_t* step,
                     void* stream);
 int mesm_clip_grad(float* g, int64_t n, const float* partials, int32_t np, float max_norm,
@@ -907,6 +928,9 @@ int mesm_adamw_step(float* p, const float* g, float* m, float* v, const uint8_t*
                     const float* partials, int32_t np, float max_norm, const float* lr, float beta1,
                     float beta2, float eps, float weight_decay, const int32_t* step, float* norm_out,
                     void* stream);
+int mesm_adamw_step_groups(float* p, const float* g, float* m, float* v, const uint8_t* tag4, int64_t n,
+                           const float* partials, int32_t np, float max_norm, const MesmAdamGroup* groups,
+                           int32_t n_groups, const int32_t* step, float* norm_out, void* stream);
 
 /* ------------------------------------------------------------------------- */
 /*

@@ -129,6 +129,14 @@ class CritBwdArgs(ctypes.Structure):
     ]
 
 
+class AdamGroup(ctypes.Structure):
+    """MesmAdamGroup: one row of FlatAdamW's device-side hyperparameter table"""
+    _fields_ = [("lr", ctypes.c_float), ("beta1", ctypes.c_float), ("beta2", ctypes.c_float), ("eps", ctypes.c_float),
+                ("weight_decay", ctypes.c_float), ("step0", ctypes.c_int32), ("pad", ctypes.c_int32 * 2)]
+
+
+ADAM_MAX_GROUPS = 64
+
 # name -> (restype, argtypes); mirrors include/mesm_gfx950.h one to one.
 _i32, _i64, _f32, _u32 = ctypes.c_int32, ctypes.c_int64, ctypes.c_float, ctypes.c_uint32
 PROTOTYPES = {
@@ -190,6 +198,7 @@ PROTOTYPES = {
     "mesm_clip_grad": (ctypes.c_int, [c_ptr, _i64, c_ptr, _i32, _f32, c_ptr, c_ptr]),
     "mesm_adamw_step": (ctypes.c_int, [c_ptr] * 5 + [_i64, c_ptr, _i32, _f32, c_ptr, _f32, _f32, _f32, _f32,
                                        c_ptr, c_ptr, c_ptr]),
+    "mesm_adamw_step_groups": (ctypes.c_int, [c_ptr] * 5 + [_i64, c_ptr, _i32, _f32, c_ptr, _i32, c_ptr, c_ptr, c_ptr]),
     "mesm_set_loss_fwd_layers": (ctypes.c_int, [c_ptr, c_ptr, _i32, c_ptr, c_ptr, c_ptr, _i32, _i32, _i32, _f32, _f32, _f32,
                                                 _f32, c_ptr, c_ptr, c_ptr, c_ptr]),
     "mesm_set_loss_fwd": (ctypes.c_int, [c_ptr] * 5 + [_i32, _i32, _i32, _f32, _f32, _f32, _f32, c_ptr, c_ptr, c_ptr]),

@@ -100,6 +100,77 @@ __global__ __launch_bounds__(OPT_THREADS) void adamw_kernel(
   }
 }
 
+// what adamw_kernel derives from its scalar arguments, per parameter group (32 bytes: two 16-byte LDS reads)
+struct alignas(16) GroupConsts {
+  float step_size, inv_sqrt_bc2, decay, eps, beta1, beta2, one_m_beta1, one_m_beta2;
+};
+
+// AdamW with per-group hyperparameters: tag4[i] == 0 skips group-of-4 i (a tensor no parameter group covers, or one
+// without a gradient this step), tag4[i] == k + 1 updates it with groups[k].  The constants of every group are derived
+// once per workgroup from the device table, with adamw_kernel's float expressions (one group over the whole buffer gives
+// adamw_kernel's bits), and kept in LDS; the per-element work is adamw_kernel's plus that indexed read, which is
+// wave-uniform except where two tensors of different groups meet inside a wave.
+__global__ __launch_bounds__(OPT_THREADS) void adamw_groups_kernel(
+    float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+    const uint8_t* __restrict__ tag4, int64_t n4, const float* __restrict__ partials, int np, float max_norm,
+    const MesmAdamGroup* __restrict__ groups, int n_groups, const int32_t* __restrict__ step,
+    float* __restrict__ norm_out) {
+  __shared__ float sh[OPT_THREADS / 64];
+  __shared__ GroupConsts gc[MESM_ADAM_MAX_GROUPS];
+  __shared__ uint32_t live[MESM_ADAM_MAX_GROUPS];  // 0: a group that has not seen a step yet (t < 1) is skipped
+  float coef = 1.0f;
+  if (max_norm > 0.0f) {
+    const float norm = total_norm(partials, np, sh);
+    if (blockIdx.x == 0 && threadIdx.x == 0 && norm_out) norm_out[0] = norm;
+    coef = fminf(max_norm / (norm + 1e-6f), 1.0f);
+  }
+  if ((int)threadIdx.x < n_groups) {
+    const MesmAdamGroup h = groups[threadIdx.x];
+    const int32_t ti = step[0] - h.step0;
+    const float lr = h.lr, beta1 = h.beta1, beta2 = h.beta2, wd = h.weight_decay;
+    const float t = (float)(ti < 1 ? 1 : ti);  // (a skipped group divides nothing by zero)
+    const float bc1 = 1.0f - powf(beta1, t);
+    const float bc2 = 1.0f - powf(beta2, t);
+    GroupConsts c;
+    c.step_size = lr / bc1;
+    c.inv_sqrt_bc2 = 1.0f / sqrtf(bc2);
+    c.decay = 1.0f - lr * wd;
+    c.eps = h.eps;
+    c.beta1 = beta1;
+    c.beta2 = beta2;
+    c.one_m_beta1 = 1.0f - beta1;
+    c.one_m_beta2 = 1.0f - beta2;
+    gc[threadIdx.x] = c;
+    live[threadIdx.x] = ti >= 1;
+  }
+  __syncthreads();
+  for (int64_t i = (int64_t)blockIdx.x * OPT_THREADS + threadIdx.x; i < n4; i += (int64_t)gridDim.x * OPT_THREADS) {
+    const uint32_t k = (uint32_t)tag4[i] - 1u;  // tag 0 wraps past every group
+    if (k >= (uint32_t)n_groups) continue;
+    const GroupConsts c = gc[k];
+    const uint32_t alive = live[k];  // (looked at after the loads: no LDS round trip in front of them)
+    float4 pv = reinterpret_cast<float4*>(p)[i];
+    const float4 gv = reinterpret_cast<const float4*>(g)[i];
+    float4 mv = reinterpret_cast<float4*>(m)[i];
+    float4 vv = reinterpret_cast<float4*>(v)[i];
+    float pe[4] = {pv.x, pv.y, pv.z, pv.w}, ge[4] = {gv.x, gv.y, gv.z, gv.w};
+    float me[4] = {mv.x, mv.y, mv.z, mv.w}, ve[4] = {vv.x, vv.y, vv.z, vv.w};
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const float gg = ge[e] * coef;
+      pe[e] *= c.decay;
+      me[e] = c.beta1 * me[e] + c.one_m_beta1 * gg;
+      ve[e] = c.beta2 * ve[e] + c.one_m_beta2 * gg * gg;
+      const float denom = sqrtf(ve[e]) * c.inv_sqrt_bc2 + c.eps;
+      pe[e] -= c.step_size * (me[e] / denom);
+    }
+    if (!alive) continue;
+    reinterpret_cast<float4*>(p)[i] = make_float4(pe[0], pe[1], pe[2], pe[3]);
+    reinterpret_cast<float4*>(m)[i] = make_float4(me[0], me[1], me[2], me[3]);
+    reinterpret_cast<float4*>(v)[i] = make_float4(ve[0], ve[1], ve[2], ve[3]);
+  }
+}
+
 inline int opt_blocks(int64_t n4) {
   int64_t b = (n4 + OPT_THREADS - 1) / OPT_THREADS;
   if (b > 1024) b = 1024;
@@ -135,5 +206,19 @@ extern "C" int mesm_adamw_step(float* p, const float* g, float* m, float* v, con
   if ((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) != 0) return MESM_EALIGN;
   hipLaunchKernelGGL(adamw_kernel, dim3(opt_blocks(n / 4)), dim3(OPT_THREADS), 0, (hipStream_t)stream, p, g, m, v,
                      active4, n / 4, partials, np, max_norm, lr, beta1, beta2, eps, weight_decay, step, norm_out);
+  return mesm_launch_status();
+}
+
+extern "C" int mesm_adamw_step_groups(float* p, const float* g, float* m, float* v, const uint8_t* tag4, int64_t n,
+                                      const float* partials, int32_t np, float max_norm,
+                                      const MesmAdamGroup* groups, int32_t n_groups, const int32_t* step,
+                                      float* norm_out, void* stream) {
+  if (!p || !g || !m || !v || !tag4 || !groups || !step || n <= 0 || (n & 3)) return MESM_EINVAL;
+  if (n_groups < 1 || n_groups > MESM_ADAM_MAX_GROUPS) return MESM_EINVAL;
+  if (max_norm > 0.f && (!partials || np <= 0 || np > 1024)) return MESM_EINVAL;
+  if ((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) != 0) return MESM_EALIGN;
+  if (((uintptr_t)groups & 3) != 0) return MESM_EALIGN;
+  hipLaunchKernelGGL(adamw_groups_kernel, dim3(opt_blocks(n / 4)), dim3(OPT_THREADS), 0, (hipStream_t)stream, p, g, m,
+                     v, tag4, n / 4, partials, np, max_norm, groups, n_groups, step, norm_out);
   return mesm_launch_status();
 }

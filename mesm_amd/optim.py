@@ -19,6 +19,17 @@ Drop-in use in the reference loop:
     optimizer.step(grad_clip=opt.grad_clip)     # replaces clip_grad_norm_ + optimizer.step()
 
 `clip_grad_norm_(model, max_norm)` is also provided for loops that keep the two calls apart.
+
+Parameter groups (the `param_dicts` form of runner.py:349) and partial coverage:
+
+    groups = param_groups(model, [("transformer.decoder.", dict(lr=0.1 * opt.lr)),
+                                  ("ss_reconstructor.", dict(freeze=True))],
+                          no_decay_1d=True, lr=opt.lr, weight_decay=opt.weight_decay)
+    optimizer = FlatAdamW(model, params=groups)                  # or params=[some parameters]
+
+Still two launches: one tag byte per 4 elements of the flat layout names the group (0: not covered, or no
+gradient this step), and lr / betas / eps / weight_decay of every group live in a small device table, so
+a captured `step()` follows what schedulers and users write into `param_groups`.
 """
 import ctypes
 
@@ -48,26 +59,131 @@ def clip_grad_norm_(model, max_norm):
     return norm[0]
 
 
+_HYPER = ("lr", "betas", "eps", "weight_decay")
+_TABLE_SLOTS = 4  # pinned staging copies of the hyperparameter table in flight at once
+
+
+def tag_table(gb, group_of, has_grad):
+    """The uint8 table mesm_adamw_step_groups reads, on the host: one byte per 4 elements of the flat layout
+    (gradbuf.py pads every tensor to a multiple of 4, so no byte belongs to two tensors), group index + 1 over the
+    padded range of every tensor that sits in a group AND has a gradient, 0 everywhere else."""
+    tags = torch.zeros(gb.numel // 4, dtype=torch.uint8)
+    for p, off, k, on in zip(gb.params, gb.offsets, group_of, has_grad):
+        if on and k >= 0:
+            tags[off // 4:(off + p.numel() + 3) // 4] = k + 1
+    return tags
+
+
+def _v_scale(beta2, t):
+    """exp_avg_sq of torch.optim.AdamW over exp_avg_sq of the kernels after t steps on the same gradients.  The kernels
+    take beta2 as a float and weigh g^2 with 1.0f - beta2 (for 0.999: 1.3e-5 below torch's 0.001) next to a bias
+    correction from the same float, so their v / (1 - beta2^t) is torch's although their raw v is not; a state dict
+    carries the raw moment across, and this factor keeps the bias-corrected one -- what the update uses -- intact."""
+    if t < 1:
+        return 1.0
+    b2f = ctypes.c_float(beta2).value
+    return (1.0 - beta2 ** t) / (1.0 - b2f ** t)
+
+
 class FlatAdamW(torch.optim.Optimizer):
     """torch.optim.AdamW semantics (decoupled weight decay, bias correction, eps outside the sqrt of
-    the bias-corrected second moment, amsgrad off) over flat buffers."""
+    the bias-corrected second moment, amsgrad off) over flat buffers.
 
-    def __init__(self, model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2):
+    `params=None` covers every tensor of `model.gradbuf()` with one set of hyperparameters (one launch of
+    mesm_adamw_step).  `params` may also be an iterable of parameters (a subset: the rest of the model is never
+    touched) or a list of torch-style group dicts with their own lr / betas / eps / weight_decay (at most 64;
+    `param_groups()` below builds such a list from name rules); the update is then mesm_adamw_step_groups, which
+    reads every group's hyperparameters from a small device table.  Groups are honoured or refused (ValueError),
+    never ignored: a tensor the flat buffers do not hold, a tensor in two groups, amsgrad, maximize.
+
+    The table is uploaded by `sync_hyperparameters()` only when `param_groups` changed on the host (a scheduler,
+    or the user editing weight_decay / betas / eps), into the SAME device tensor: `step()` calls it; a caller that
+    replays a captured `step()` calls it before the replay.  Hyperparameter changes never need a new capture.  A
+    MEMBERSHIP change does (`add_param_group`, or another set of tensors without a gradient): the tag table is
+    rebuilt on the host.
+
+    `state_dict()` / `load_state_dict()` speak torch.optim.AdamW's format with the same grouping, in both directions;
+    with groups, exp_avg_sq is written in torch's convention (`_v_scale`)."""
+
+    def __init__(self, model, params=None, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2,
+                 amsgrad=False, maximize=False):
         self.model = model
         gb = model.gradbuf()
-        params = list(gb.params)
-        super().__init__([{"params": params}], dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
         self.gb = gb
+        self._index = {id(p): i for i, p in enumerate(gb.params)}
+        self._group_of = [-1] * len(gb.params)  # parameter (gradbuf order) -> its group, -1: not covered
+        self._step0 = []  # per group: the global step count when it joined
+        self._grouped = params is not None
         self.flat_p = self.exp_avg = self.exp_avg_sq = None
         self.step_t = self.lr_t = None
         self._active = None
         self._active_key = None
+        self._table = self._table_host = self._table_events = None
+        self._table_slot = 0
+        self._hyper_host = None
         self.last_norm = None
-        if params[0].is_cuda:
+        if params is None:
+            groups = [{"params": list(gb.params)}]
+        else:
+            groups = list(params)
+            if groups and not isinstance(groups[0], dict):
+                groups = [{"params": groups}]
+        super().__init__(groups, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad,
+                                      maximize=maximize))
+        if gb.params[0].is_cuda:
             # the flat state is created NOW, not at the first step(): a HIP graph captured after this
             # constructor sees the final parameter addresses (model.flat_params is idempotent and
             # build_model has normally done it already)
             self._ensure()
+
+    # ------------------------------------------------------------------ groups
+    def _name_of(self, p):
+        i = self._index.get(id(p))
+        if i is not None:
+            return self.gb.names[i]
+        for n, q in self.model.named_parameters():
+            if q is p:
+                return n
+        return "<a %s tensor that is no parameter of the model>" % (tuple(p.shape),)
+
+    def add_param_group(self, param_group):
+        """torch's add_param_group with the checks of the constructor.  A group added after construction starts its
+        bias correction at t = 1 (step0 = the current step count) on zeroed moments, like torch's per-parameter
+        `step`.  A captured step() must be captured again afterwards (the set of updated tensors changed)."""
+        if not isinstance(param_group, dict):
+            raise TypeError("param_group must be a dict")
+        ps = param_group["params"]
+        param_group = dict(param_group, params=[ps] if isinstance(ps, torch.Tensor) else list(ps))
+        k = len(self._step0)
+        if k >= _lib.ADAM_MAX_GROUPS:
+            raise ValueError("FlatAdamW takes at most %d parameter groups (group %d starts with %s)"
+                             % (_lib.ADAM_MAX_GROUPS, k, self._name_of(param_group["params"][0])
+                                if param_group["params"] else "no parameter"))
+        seen = set()
+        for p in param_group["params"]:
+            i = self._index.get(id(p))
+            if i is None:
+                raise ValueError("parameter %s is not in the model's flat buffers (not a parameter of this model, or "
+                                 "requires_grad was False when the model was built)" % self._name_of(p))
+            if self._group_of[i] >= 0 or i in seen:
+                raise ValueError("parameter %s appears in more than one parameter group" % self.gb.names[i])
+            seen.add(i)
+        merged = dict(self.defaults, **param_group)
+        for flag in ("amsgrad", "maximize"):
+            if merged.get(flag):
+                raise ValueError("FlatAdamW has no %s (group %d, which starts with %s)"
+                                 % (flag, k, self._name_of(merged["params"][0]) if merged["params"] else "no parameter"))
+        super().add_param_group(param_group)
+        step0 = int(self.step_t.item()) if self.step_t is not None else 0
+        self._step0.append(step0)
+        for i in seen:
+            self._group_of[i] = k
+            if self.exp_avg is not None:
+                sl = slice(self.gb.offsets[i], self.gb.offsets[i] + self.gb.params[i].numel())
+                self.exp_avg[sl].zero_()
+                self.exp_avg_sq[sl].zero_()
+        self._active_key = None
+        self._hyper_host = None
 
     # ------------------------------------------------------------------ flat state
     def _ensure(self):
@@ -82,6 +198,15 @@ class FlatAdamW(torch.optim.Optimizer):
         self.exp_avg_sq = torch.zeros_like(self.flat_p)
         self.step_t = torch.zeros(1, device=dev, dtype=torch.int32)
         self.lr_t = torch.full((1,), float(self.param_groups[0]["lr"]), device=dev, dtype=torch.float32)
+        if self._grouped:
+            nbytes = _lib.ADAM_MAX_GROUPS * ctypes.sizeof(_lib.AdamGroup)
+            self._table = torch.zeros(nbytes, device=dev, dtype=torch.uint8)
+            self._table_host = torch.zeros(_TABLE_SLOTS, nbytes, dtype=torch.uint8)
+            if dev.type == "cuda":
+                self._table_host = self._table_host.pin_memory()
+            self._table_events = [None] * _TABLE_SLOTS
+            self._hyper_host = None
+            self._active = self._active_key = None
 
     def _active_mask(self):
         """groups of 4 elements that belong to a parameter whose .grad is not None this step"""
@@ -96,18 +221,68 @@ class FlatAdamW(torch.optim.Optimizer):
             self._active_key = key
         return self._active
 
+    def _tags(self):
+        """tag_table() on the device, rebuilt when the set of tensors with a gradient (or a group's membership)
+        changed; always the same device tensor"""
+        key = tuple(p.grad is not None for p in self.gb.params)
+        if key != self._active_key:
+            tags = tag_table(self.gb, self._group_of, key)
+            if self._active is None:
+                self._active = tags.to(self.flat_p.device)
+            else:
+                self._active.copy_(tags)
+            self._active_key = key
+        return self._active
+
+    def _hyper(self):
+        res = []
+        for g, step0 in zip(self.param_groups, self._step0):
+            if g.get("amsgrad") or g.get("maximize"):
+                raise ValueError("FlatAdamW has no amsgrad / maximize (group that starts with %s)"
+                                 % self._name_of(g["params"][0]))
+            b1, b2 = g["betas"]
+            res.append((float(g["lr"]), float(b1), float(b2), float(g["eps"]), float(g["weight_decay"]), step0))
+        return res
+
+    def sync_hyperparameters(self):
+        """Bring the device-side hyperparameters up to date with `param_groups` (schedulers and users edit those on
+        the host).  Costs a comparison of a few floats per group when nothing changed; otherwise one small copy from
+        a pinned buffer into the same device tensor, so a captured step() sees the new values at its next replay."""
+        self._ensure()
+        if not self._grouped:
+            g = self.param_groups[0]
+            if float(g["lr"]) != getattr(self, "_lr_host", None):  # StepLR edits param_groups[0]["lr"]
+                self._lr_host = float(g["lr"])
+                self.lr_t.fill_(self._lr_host)
+            return
+        hyper = self._hyper()
+        if hyper == self._hyper_host:
+            return
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("the hyperparameters changed: call sync_hyperparameters() before capturing step()")
+        slot = self._table_slot
+        self._table_slot = (slot + 1) % _TABLE_SLOTS
+        if self._table_events[slot] is None:
+            self._table_events[slot] = torch.cuda.Event()
+        else:
+            self._table_events[slot].synchronize()  # (the copy that last read this slot: long done)
+        host = self._table_host[slot]
+        rows = (_lib.AdamGroup * _lib.ADAM_MAX_GROUPS).from_address(host.data_ptr())
+        for row, (lr, b1, b2, eps, wd, step0) in zip(rows, hyper):
+            row.lr, row.beta1, row.beta2, row.eps, row.weight_decay, row.step0 = lr, b1, b2, eps, wd, step0
+        self._table.copy_(host, non_blocking=True)
+        self._table_events[slot].record()
+        self._hyper_host = hyper
+
     # ------------------------------------------------------------------ optimizer protocol
     @torch.no_grad()
     def step(self, closure=None, grad_clip=0.0):
-        """grad_clip > 0 fuses nn.utils.clip_grad_norm_(params, grad_clip) into the update (the
-        gradients themselves are left unscaled)."""
+        """grad_clip > 0 fuses nn.utils.clip_grad_norm_(model.parameters(), grad_clip) into the update (the
+        gradients themselves are left unscaled).  The norm is that of the WHOLE flat gradient buffer, whichever
+        tensors this optimizer covers."""
         assert closure is None
-        self._ensure()
-        g = self.param_groups[0]
-        if float(g["lr"]) != getattr(self, "_lr_host", None):  # StepLR edits param_groups[0]["lr"]
-            self._lr_host = float(g["lr"])
-            self.lr_t.fill_(self._lr_host)
-        active = self._active_mask()
+        self.sync_hyperparameters()
+        active = self._tags() if self._grouped else self._active_mask()
         if grad_clip and grad_clip > 0:
             partials, n_p = _sumsq(self.gb, self.step_t)
             self.last_norm = torch.empty(1, device=self.flat_p.device, dtype=torch.float32)
@@ -115,6 +290,14 @@ class FlatAdamW(torch.optim.Optimizer):
             partials, n_p = None, 0
             self.step_t += 1
             self.last_norm = None
+        if self._grouped:
+            check(lib().mesm_adamw_step_groups(ptr(self.flat_p), ptr(self.gb.flat), ptr(self.exp_avg),
+                                               ptr(self.exp_avg_sq), ptr(active), self.flat_p.numel(), ptr(partials),
+                                               n_p, float(grad_clip or 0.0), ptr(self._table), len(self._step0),
+                                               ptr(self.step_t), ptr(self.last_norm), stream_ptr()),
+                  "mesm_adamw_step_groups")
+            return
+        g = self.param_groups[0]
         b1, b2 = g["betas"]
         check(lib().mesm_adamw_step(ptr(self.flat_p), ptr(self.gb.flat), ptr(self.exp_avg), ptr(self.exp_avg_sq),
                                     ptr(active), self.flat_p.numel(), ptr(partials), n_p,
@@ -126,34 +309,107 @@ class FlatAdamW(torch.optim.Optimizer):
         self.model.zero_grad(set_to_none=set_to_none)
 
     # ------------------------------------------------------------------ checkpoints (torch.optim.AdamW format)
+    def _members(self):
+        """per group: [(parameter, offset)] in the group's own order -- torch numbers the parameters of a state dict
+        through the groups in order"""
+        return [[(p, self.gb.offsets[self._index[id(p)]]) for p in g["params"]] for g in self.param_groups]
+
     def state_dict(self):
         self._ensure()
         step = int(self.step_t.item())
-        state = {}
-        for i, (p, off) in enumerate(zip(self.gb.params, self.gb.offsets)):
-            sl = slice(off, off + p.numel())
-            state[i] = {"step": torch.tensor(float(step)),
-                        "exp_avg": self.exp_avg[sl].view(p.shape).clone(),
-                        "exp_avg_sq": self.exp_avg_sq[sl].view(p.shape).clone()}
-        groups = [{k: v for k, v in self.param_groups[0].items() if k != "params"}]
-        groups[0]["params"] = list(range(len(self.gb.params)))
+        state, groups, i = {}, [], 0
+        for g, members, step0 in zip(self.param_groups, self._members(), self._step0):
+            for p, off in members:
+                sl = slice(off, off + p.numel())
+                v = self.exp_avg_sq[sl].view(p.shape).clone()
+                if self._grouped:  # (the default form keeps writing the raw moment, as it always has)
+                    v *= _v_scale(g["betas"][1], step - step0)
+                state[i] = {"step": torch.tensor(float(step - step0)),
+                            "exp_avg": self.exp_avg[sl].view(p.shape).clone(), "exp_avg_sq": v}
+                i += 1
+            out = {k: v for k, v in g.items() if k != "params"}
+            out["params"] = list(range(i - len(members), i))
+            groups.append(out)
         return {"state": state, "param_groups": groups}
 
     def load_state_dict(self, sd):
         self._ensure()
-        step = 0
-        for i, (p, off) in enumerate(zip(self.gb.params, self.gb.offsets)):
-            st = sd["state"].get(i)
-            if st is None:
-                continue
-            sl = slice(off, off + p.numel())
-            self.exp_avg[sl].copy_(st["exp_avg"].reshape(-1))
-            self.exp_avg_sq[sl].copy_(st["exp_avg_sq"].reshape(-1))
-            step = max(step, int(float(st["step"])))
-        self.step_t.fill_(step)
-        for k, v in sd["param_groups"][0].items():
-            if k != "params":
-                self.param_groups[0][k] = v
+        saved = sd["param_groups"]
+        members = self._members()
+        if len(saved) != len(members):
+            raise ValueError("loaded state dict has %d parameter groups, the optimizer has %d" % (len(saved), len(members)))
+        for k, (sg, ms) in enumerate(zip(saved, members)):
+            if len(sg["params"]) != len(ms):
+                raise ValueError("loaded state dict's group %d has %d parameters, the optimizer's has %d"
+                                 % (k, len(sg["params"]), len(ms)))
+            if sg.get("amsgrad") or sg.get("maximize"):
+                raise ValueError("FlatAdamW has no amsgrad / maximize (loaded group %d, which starts with %s)"
+                                 % (k, self._name_of(ms[0][0])))
+        group_step = []
+        for sg, ms in zip(saved, members):
+            step = 0
+            for pid, (p, off) in zip(sg["params"], ms):
+                st = sd["state"].get(pid)
+                if st is None:
+                    continue
+                sl = slice(off, off + p.numel())
+                self.exp_avg[sl].copy_(st["exp_avg"].reshape(-1))
+                self.exp_avg_sq[sl].copy_(st["exp_avg_sq"].reshape(-1))
+                if self._grouped:
+                    self.exp_avg_sq[sl] /= _v_scale(sg.get("betas", self.defaults["betas"])[1], int(float(st["step"])))
+                step = max(step, int(float(st["step"])))
+            group_step.append(step)
+        total = max(group_step)
+        self.step_t.fill_(total)
+        self._step0 = [total - s for s in group_step]
+        for g, sg in zip(self.param_groups, saved):
+            for k, v in sg.items():
+                if k != "params":
+                    g[k] = v
+        self._hyper_host = None
+
+
+def param_groups(model, rules=(), no_decay_1d=False, **defaults):
+    """Torch-style group dicts over the trainable tensors of `model`, for FlatAdamW(model, params=...) or
+    torch.optim.AdamW.
+
+    rules: a sequence of (pattern, options).  `pattern` is a name prefix (str) or a compiled regex (`.search` on the
+    named_parameters() name); the FIRST matching rule takes the tensor.  `options` holds any of lr, weight_decay,
+    betas, eps, which override `defaults` for that group, or freeze=True: those tensors are left out of every group.
+    Tensors no rule matches form the first group, with `defaults` alone.  With no_decay_1d, the tensors with
+    ndim <= 1 (biases, LayerNorm, PReLU slopes) of each group move to a twin group right behind it with
+    weight_decay = 0.  Empty groups are dropped."""
+    known = set(_HYPER) | {"freeze"}
+    for key in defaults:
+        if key not in _HYPER:
+            raise ValueError("unknown default %r (one of %s)" % (key, ", ".join(_HYPER)))
+    rules = list(rules)
+    for pattern, options in rules:
+        if not isinstance(pattern, str) and not hasattr(pattern, "search"):
+            raise ValueError("a rule's pattern is a name prefix or a compiled regex, not %r" % (pattern,))
+        for key in options:
+            if key not in known:
+                raise ValueError("unknown option %r in the rule for %r (one of %s)"
+                                 % (key, pattern, ", ".join(sorted(known))))
+    buckets = [dict(defaults, params=[])]
+    for _, options in rules:
+        buckets.append(dict(defaults, params=[], **{k: v for k, v in options.items() if k != "freeze"}))
+    gb = model.gradbuf()
+    for name, p in zip(gb.names, gb.params):
+        hit = next((r for r, (pattern, _) in enumerate(rules)
+                    if (name.startswith(pattern) if isinstance(pattern, str) else pattern.search(name))), None)
+        if hit is None:
+            buckets[0]["params"].append(p)
+        elif not rules[hit][1].get("freeze"):
+            buckets[hit + 1]["params"].append(p)
+    groups = []
+    for b in buckets:
+        if no_decay_1d:
+            groups.append(dict(b, params=[p for p in b["params"] if p.ndim > 1]))
+            groups.append(dict(b, params=[p for p in b["params"] if p.ndim <= 1], weight_decay=0.0))
+        else:
+            groups.append(b)
+    return [g for g in groups if g["params"]]
 
 
 def build_optimizer(opt, model):
