@@ -150,13 +150,28 @@ int mesm_gemm_group(const MesmGemmArgs* args, int32_t n, void* stream);
  * mesm_gemm_flush_side reduces whatever is still pending with plain launches: call it before dslope is read or
  * dslope_ws is released without another GEMM launch in between. */
 int mesm_gemm_flush_side(void* stream);
-/* Tuning tools only: the dispatch switches MESM_GEMM_TILE / MESM_GEMM_BF16X are read from the environment ONCE, when the
+/* Tuning tools and tests: the dispatch switches MESM_GEMM_TILE / MESM_GEMM_BF16X are read from the environment ONCE, when the
  * library is loaded; this entry changes them between calls of one process (a negative value keeps the current one). */
 int mesm_gemm_set_switches(int32_t force_tile, int32_t bf16x);
 /* The GEMM arithmetic in force: 2 = f32 products as THREE fp16 matrix products over operands split into two fp16 terms under a
  * wave-owned power-of-two scale (the default since round 6, csrc/gemm_ws.hpp), 6 = six bf16 matrix products over operands split
  * exactly into three bf16 terms (round 4), 0 = every product on the f32 matrix instruction (what bench.py reports as `dtype`). */
 int mesm_gemm_get_bf16x(void);
+/* The forced kernel in force (MESM_GEMM_TILE; 0 = the automatic choice): what a caller restores after mesm_gemm_set_switches. */
+int mesm_gemm_get_force_tile(void);
+/*
+ * What a call would turn into, without launching anything (no device is touched: pointers are read for null-ness and
+ * alignment only).  n >= 1: the grouped call mesm_gemm_group(args, n); n == 0: the single call mesm_gemm_f32(args).
+ * Writes four int32 per problem, out[4 * i ..] for args[i]:
+ *   position  in the call's issue order (longest reduce slice first),
+ *   family    0 | 1 | 2 register-staged tile 32 | 64 | 128, 3 frag, 4 wstage (k-split 32 x 32), 5 wstage64 (k-split
+ *             64 x 64), 6 wtall (96 x 32), 7 lds64 (64 x 64 LDS-DMA ring),
+ *   variant   the template variant launched: xf | stages << 1 | bf << 3 | mask << 6 | vec << 10 | add << 13 | grouped << 15
+ *             (operand-transform bodies; wstage k-tiles per wave; wstage64 split arithmetic; operand-layout pairs of a
+ *             grouped kernel; load width and addend operand of the tiles / frag; the grouped kernel of the family),
+ *   launch    index, in issue order, of the launch the problem shares.
+ */
+int mesm_gemm_plan(const MesmGemmArgs* args, int32_t n, int32_t* out);
 /* Forget the pending reductions without running them (error paths: their workspaces may already be released). */
 int mesm_gemm_drop_side(void);
 

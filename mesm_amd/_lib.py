@@ -146,6 +146,8 @@ PROTOTYPES = {
     "mesm_gemm_group": (ctypes.c_int, [ctypes.POINTER(GemmArgs), _i32, c_ptr]),
     "mesm_gemm_flush_side": (ctypes.c_int, [c_ptr]),
     "mesm_gemm_get_bf16x": (ctypes.c_int, []),
+    "mesm_gemm_get_force_tile": (ctypes.c_int, []),
+    "mesm_gemm_plan": (ctypes.c_int, [ctypes.POINTER(GemmArgs), _i32, ctypes.POINTER(ctypes.c_int32)]),
     "mesm_gemm_set_switches": (ctypes.c_int, [_i32, _i32]),
     "mesm_gemm_drop_side": (ctypes.c_int, []),
     "mesm_gemm_tape": (ctypes.c_int, [_i32]),

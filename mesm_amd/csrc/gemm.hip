@@ -12,6 +12,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <utility>
+#include <type_traits>
 #include <vector>
 
 #include <cstddef>
@@ -21,8 +22,6 @@
 
 namespace {
 
-int mesm_gemm_force_tile();  // MESM_GEMM_TILE / MESM_GEMM_BF16X, read once at load (definitions next to dispatch)
-int mesm_gemm_bf16x();
 
 __global__ __launch_bounds__(256) void dslope_reduce_kernel(const float* __restrict__ ws, int64_t n,
                                                             float* __restrict__ dst) {
@@ -42,11 +41,10 @@ struct SidePending {
   hipStream_t stream;  // the stream the producing launch went to: only a launch on the SAME stream may carry it
 };
 std::vector<SidePending> g_side;
-const bool g_side_on = getenv("MESM_DSLOPE_LAUNCH") == nullptr;  // MESM_DSLOPE_LAUNCH=1: one launch per reduction (A/B)
 
 inline int dslope_finish_n(const MesmGemmArgs& a, int64_t n, hipStream_t s) {
   if (a.e_actgrad != MESM_ACT_PRELU || !a.dslope) return MESM_OK;
-  if (g_side_on && n < (1 << 30)) {
+  if (n < (1 << 30)) {  // carried by the next GEMM launch on the stream (take_side)
     g_side.push_back({a.dslope_ws, a.dslope, (int)n, s});
     return MESM_OK;
   }
@@ -485,57 +483,6 @@ __global__ __launch_bounds__(NTHREADS) void gemm_f32_kernel(const MesmGemmArgs p
   if (p.e_actgrad == MESM_ACT_PRELU && p.dslope) dslope_store(p, dslope_part, Red, linear_block());
 }
 
-template <int BM, int BN, int LA, int LB, int VEC, int ADD>
-int launch(const MesmGemmArgs& a, hipStream_t s) {
-  // 64x64 tiles run few MFMAs per k-step: a deeper k-step (64) keeps the MFMA block longer than
-  // the global-load latency it has to hide; 128x128 tiles already do with 32.
-  constexpr int BK = (BM == 128) ? 32 : 64;
-  dim3 grid((a.M + BM - 1) / BM, (a.N + BN - 1) / BN, a.split_k > 1 ? a.split_k : 1);
-  hipLaunchKernelGGL((gemm_f32_kernel<BM, BN, BK, LA, LB, VEC, ADD>), grid, dim3(NTHREADS), 0, s, a);
-  const int rc = mesm_launch_status();
-  return rc != MESM_OK ? rc : dslope_finish(a, grid, s);
-}
-
-template <int BM, int BN, int VEC, int ADD>
-int launch_layout(const MesmGemmArgs& a, hipStream_t s) {
-  constexpr int R = MESM_LAYOUT_REDUCE_CONTIG, O = MESM_LAYOUT_OUTER_CONTIG;
-  if (a.a_layout == R && a.b_layout == R) return launch<BM, BN, R, R, VEC, ADD>(a, s);
-  if (a.a_layout == R && a.b_layout == O) return launch<BM, BN, R, O, VEC, ADD>(a, s);
-  if (a.a_layout == O && a.b_layout == O) return launch<BM, BN, O, O, VEC, ADD>(a, s);
-  if (a.a_layout == O && a.b_layout == R) return launch<BM, BN, O, R, VEC, ADD>(a, s);
-  return MESM_EINVAL;
-}
-
-template <int VEC>
-int launch_tile(const MesmGemmArgs& a, hipStream_t s) {
-  const int add = a.A2 ? 1 : (a.B2 ? 2 : 0);
-  const long z = a.split_k > 1 ? a.split_k : 1;
-  auto blocks = [&](int t) { return (long)((a.M + t - 1) / t) * ((a.N + t - 1) / t) * z; };
-  // tuning knob (tools/gemm_bench4.py): MESM_GEMM_TILE=32|64|128 pins the configuration
-  const int force_tile = mesm_gemm_force_tile();
-  if (force_tile == 128 && add == 0) return launch_layout<128, 128, VEC, 0>(a, s);
-  if (force_tile == 64) {
-    if (add == 0) return launch_layout<64, 64, VEC, 0>(a, s);
-    if (add == 1) return launch_layout<64, 64, VEC, 1>(a, s);
-    return launch_layout<64, 64, VEC, 2>(a, s);
-  }
-  if (force_tile == 32) {
-    if (add == 0) return launch_layout<32, 32, VEC, 0>(a, s);
-    if (add == 1) return launch_layout<32, 32, VEC, 1>(a, s);
-    return launch_layout<32, 32, VEC, 2>(a, s);
-  }
-  // largest tile that still gives every CU about two workgroups; the small 32x32 k-split tile
-  // otherwise (most d x d GEMMs of the step: 2400 x 256 x 256 -> 600 workgroups)
-  if (blocks(128) >= 512 && add == 0) return launch_layout<128, 128, VEC, 0>(a, s);
-  if (blocks(64) >= 512) {
-    if (add == 0) return launch_layout<64, 64, VEC, 0>(a, s);
-    if (add == 1) return launch_layout<64, 64, VEC, 1>(a, s);
-    return launch_layout<64, 64, VEC, 2>(a, s);
-  }
-  if (add == 0) return launch_layout<32, 32, VEC, 0>(a, s);
-  if (add == 1) return launch_layout<32, 32, VEC, 1>(a, s);
-  return launch_layout<32, 32, VEC, 2>(a, s);
-}
 
 // ------------------------------------------------------------------------------------------------
 // Small-problem kernel ("frag"): one 32x32 output tile per workgroup, the reduce range split over
@@ -745,32 +692,6 @@ __global__ __launch_bounds__(NTHREADS) void gemm_frag_kernel(const MesmGemmArgs 
   ksplit_epilogue<LA, LB, XF>(p, acc, Red, m0, n0, slope, seed_off, blockIdx.z, linear_block(), p.K, XForm{}, XForm{});
 }
 
-template <int LA, int LB>
-int launch_frag_add(const MesmGemmArgs& a, hipStream_t s) {
-  dim3 grid((a.M + 31) / 32, (a.N + 31) / 32, a.split_k > 1 ? a.split_k : 1);
-  const int add = a.A2 ? 1 : (a.B2 ? 2 : 0);
-  const bool xf = a.a_act != MESM_ACT_NONE || a.b_act != MESM_ACT_NONE || a.a_drop_p > 0.f || a.b_drop_p > 0.f;
-  if (xf) {
-    if (add == 0) hipLaunchKernelGGL((gemm_frag_kernel<LA, LB, 0, true>), grid, dim3(NTHREADS), 0, s, a);
-    else if (add == 1) hipLaunchKernelGGL((gemm_frag_kernel<LA, LB, 1, true>), grid, dim3(NTHREADS), 0, s, a);
-    else hipLaunchKernelGGL((gemm_frag_kernel<LA, LB, 2, true>), grid, dim3(NTHREADS), 0, s, a);
-  } else {
-    if (add == 0) hipLaunchKernelGGL((gemm_frag_kernel<LA, LB, 0, false>), grid, dim3(NTHREADS), 0, s, a);
-    else if (add == 1) hipLaunchKernelGGL((gemm_frag_kernel<LA, LB, 1, false>), grid, dim3(NTHREADS), 0, s, a);
-    else hipLaunchKernelGGL((gemm_frag_kernel<LA, LB, 2, false>), grid, dim3(NTHREADS), 0, s, a);
-  }
-  const int rc = mesm_launch_status();
-  return rc != MESM_OK ? rc : dslope_finish(a, grid, s);
-}
-
-int launch_frag(const MesmGemmArgs& a, hipStream_t s) {
-  constexpr int R = MESM_LAYOUT_REDUCE_CONTIG, O = MESM_LAYOUT_OUTER_CONTIG;
-  if (a.a_layout == R && a.b_layout == R) return launch_frag_add<R, R>(a, s);
-  if (a.a_layout == R && a.b_layout == O) return launch_frag_add<R, O>(a, s);
-  if (a.a_layout == O && a.b_layout == O) return launch_frag_add<O, O>(a, s);
-  return launch_frag_add<O, R>(a, s);
-}
-
 // the frag kernel reads reduce-contiguous operands as 16-byte vectors
 bool frag_ok(const MesmGemmArgs& a) {
   auto vec_ok = [&](const float* p, const float* p2, int64_t ld) {
@@ -797,37 +718,11 @@ bool frag_ok(const MesmGemmArgs& a) {
 //     the reader (row i, chunk c = 2s + h) finds it at position c ^ ((i >> 1) & 7) with one ds_read_b128;
 //   outer-contiguous operand: LDS row 8q + sr holds reduce index 8q + (((sr & 1) << 2) | (sr >> 1)), so
 //     that k and k + 4 (the two lane halves) sit in opposite bank halves; read with ds_read_b32.
-#ifdef MESM_L64_TRACE
-// in-kernel time stamps (s_memtime, shader cycles) of wave 0 of the first 1024 workgroups: 32 slots each
-__device__ unsigned long long l64_trace[1024 * 32];
-__device__ __forceinline__ void l64_stamp(int slot) {
-  unsigned long long t;
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-  __builtin_amdgcn_sched_barrier(0);
-  if (threadIdx.x == 0 && blockIdx.x < 1024 && blockIdx.z == 0 && slot < 32) l64_trace[blockIdx.x * 32 + slot] = t;
-}
-#define L64_STAMP(i) l64_stamp(i)
-#else
-#define L64_STAMP(i)
-#endif
-
-#ifndef MESM_WS_NW
-#define MESM_WS_NW 4
-#endif
-constexpr int WS_NW = MESM_WS_NW;  // waves per wstage workgroup = k-split factor inside the workgroup (1, 2, 4, 8).
+constexpr int WS_NW = 4;  // waves per wstage workgroup = k-split factor inside the workgroup (1, 2, 4, 8).
 // Measured (tools/gemm_sweep.py, 2400 x 256 x 256 / 4800 x 256 x 256 / 256 x 256 x 2400 split 4):
 // 4 waves 8.6 / 13.3 / 7.6 us; 2 waves 9.3 / 15.8 / 10.6; 8 waves 9.3 / 14.4 / 8.5; 1 wave 9.6 / 14.4 / 17.1.
 static_assert(WS_NW == 1 || WS_NW == 2 || WS_NW == 4 || WS_NW == 8, "wstage waves");
 constexpr int WS_THREADS = 64 * WS_NW;
-#ifndef MESM_WS_WAVES
-#define MESM_WS_WAVES 0
-#endif
-#if MESM_WS_WAVES > 0
-#define WS_BOUNDS __launch_bounds__(WS_THREADS, MESM_WS_WAVES)
-#else
-#define WS_BOUNDS __launch_bounds__(WS_THREADS)
-#endif
 
 // WS_STAGES: wave-private k-tiles resident in LDS per operand pair.  2 = double buffer (64 KB per workgroup,
 // 2 workgroups per CU), 1 = load / read / refill in place (32 KB, 5 per CU).  Measured (tools/gemm_sweep.py):
@@ -840,7 +735,6 @@ __device__ __forceinline__ void wstage_body(const MesmGemmArgs& p, const Blk blk
   const int lane = tid & 63, wave = tid >> 6;
   const int li = lane & 31, h = lane >> 5;
   const int m0 = blk.x * 32, n0 = blk.y * 32;
-  L64_STAMP(0);
 
   const int KM = gemm_kmain(p);  // reduce indices [KM, K) are added in the epilogue of the first k-slice
   int kbeg = 0, kend = KM;
@@ -883,15 +777,12 @@ __device__ __forceinline__ void wstage_body(const MesmGemmArgs& p, const Blk blk
   float csum = 0.0f;
   const bool do_colsum = (p.colsum != nullptr) && (blk.y == 0);
 
-  L64_STAMP(1);
   if (nst > 0) issue(0);
   if (WS_STAGES > 1 && nst > 1) issue(1);
-  L64_STAMP(2);
   for (int st = 0; st < nst; ++st) {
     // each stage is 8 LDS-DMA instructions; leave the next stage in flight
     if (WS_STAGES > 1 && st + 1 < nst) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    L64_STAMP(3 + 3 * st);
     const float* buf = mine + (st % WS_STAGES) * (2 * WS_SLAB);
     float a[4][4], b[4][4];
     ws_read<LA>(buf, li, h, a);
@@ -940,10 +831,8 @@ __device__ __forceinline__ void wstage_body(const MesmGemmArgs& p, const Blk blk
 #pragma unroll
         for (int j = 0; j < 4; ++j) csum += a[s_][j];
     }
-    L64_STAMP(5 + 3 * st);
   }
   asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
-  L64_STAMP(28);
 
   if (do_colsum) {
     csum = add_xor32(csum);
@@ -952,9 +841,7 @@ __device__ __forceinline__ void wstage_body(const MesmGemmArgs& p, const Blk blk
   }
   __syncthreads();  // every wave is done with its slabs: the reduction buffer aliases them
   ksplit_epilogue<LA, LB, XF, WS_NW>(p, acc, L, m0, n0, slope, seed_off, blk.z, blk.slot, KM, xa, xb);
-  L64_STAMP(29);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  L64_STAMP(30);
 }
 
 constexpr int ws_lds_floats(int stages) {  // [wave][stage][operand]; at least the cross-wave reduction buffer
@@ -970,7 +857,7 @@ inline int ws_stages_for(const MesmGemmArgs& a) {
 }
 
 template <int LA, int LB, bool XF, int STAGES>
-__global__ WS_BOUNDS void gemm_wstage_kernel(const MesmGemmArgs p, const SideRed sr) {
+__global__ __launch_bounds__(WS_THREADS) void gemm_wstage_kernel(const MesmGemmArgs p, const SideRed sr) {
   side_reduce(sr);
   __shared__ __attribute__((aligned(16))) float L[ws_lds_floats(STAGES)];
   Blk blk;
@@ -987,7 +874,7 @@ __global__ WS_BOUNDS void gemm_wstage_kernel(const MesmGemmArgs p, const SideRed
 // occur among the launch's members; only those bodies are in the kernel (the kernel with all eight is 109 KB of code: see
 // gemm_wstage64_group_kernel).
 template <int STAGES, int MASK = 15, bool XFM = true>
-__global__ WS_BOUNDS void gemm_wstage_group_kernel(const GroupArgs g, const SideRed sr) {
+__global__ __launch_bounds__(WS_THREADS) void gemm_wstage_group_kernel(const GroupArgs g, const SideRed sr) {
   side_reduce(sr);
   __shared__ __attribute__((aligned(16))) float L[ws_lds_floats(STAGES)];
   const int bid = blockIdx.x;
@@ -1022,28 +909,6 @@ __global__ WS_BOUNDS void gemm_wstage_group_kernel(const GroupArgs g, const Side
   }
 }
 
-template <int LA, int LB>
-int launch_wstage_l(const MesmGemmArgs& a, hipStream_t s) {
-  dim3 grid(((a.M + 31) / 32) * ((a.N + 31) / 32), 1, a.split_k > 1 ? a.split_k : 1);  // 1-D: xcd_tile() maps it
-  const bool xf = a.a_act != MESM_ACT_NONE || a.b_act != MESM_ACT_NONE || a.a_drop_p > 0.f || a.b_drop_p > 0.f;
-  const bool one = ws_stages_for(a) == 1;
-  const SideRed sr = take_side(s);
-  if (xf && one) hipLaunchKernelGGL((gemm_wstage_kernel<LA, LB, true, 1>), grid, dim3(WS_THREADS), 0, s, a, sr);
-  else if (xf) hipLaunchKernelGGL((gemm_wstage_kernel<LA, LB, true, 2>), grid, dim3(WS_THREADS), 0, s, a, sr);
-  else if (one) hipLaunchKernelGGL((gemm_wstage_kernel<LA, LB, false, 1>), grid, dim3(WS_THREADS), 0, s, a, sr);
-  else hipLaunchKernelGGL((gemm_wstage_kernel<LA, LB, false, 2>), grid, dim3(WS_THREADS), 0, s, a, sr);
-  const int rc = mesm_launch_status();
-  return rc != MESM_OK ? rc : dslope_finish(a, grid, s);
-}
-
-int launch_wstage(const MesmGemmArgs& a, hipStream_t s) {
-  constexpr int R = MESM_LAYOUT_REDUCE_CONTIG, O = MESM_LAYOUT_OUTER_CONTIG;
-  if (a.a_layout == R && a.b_layout == R) return launch_wstage_l<R, R>(a, s);
-  if (a.a_layout == R && a.b_layout == O) return launch_wstage_l<R, O>(a, s);
-  if (a.a_layout == O && a.b_layout == O) return launch_wstage_l<O, O>(a, s);
-  return launch_wstage_l<O, R>(a, s);
-}
-
 // LDS-DMA moves 16-byte chunks, from ANY 4-byte aligned address (measured: rows of 2818 or 5003 floats,
 // 8- and 4-byte aligned, give exact results and 51 us instead of 78 for 2400 x 256 x 2818): no alignment
 // rule on pointers or leading dimensions.  What 16-byte granularity cannot express is handled outside
@@ -1073,7 +938,6 @@ __device__ __forceinline__ void wstage64_body(const MesmGemmArgs& p, const Blk b
   const int lane = tid & 63, wave = tid >> 6;
   const int li = lane & 31, h = lane >> 5;
   const int m0 = blk.x * 64, n0 = blk.y * 64;
-  L64_STAMP(0);
 
   const int KM = gemm_kmain(p);  // reduce indices [KM, K) are added in the epilogue of the first k-slice
   int kbeg = 0, kend = KM;
@@ -1123,12 +987,9 @@ __device__ __forceinline__ void wstage64_body(const MesmGemmArgs& p, const Blk b
   HalfScales hs;  // BF == 2: this wave's operand scales (gemm_ws.hpp)
   hs.init();
 
-  L64_STAMP(1);
   if (nst > 0) issue(0);
-  L64_STAMP(2);
   for (int st = 0; st < nst; ++st) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    L64_STAMP(3 + 3 * st);
     float a[2][4][4], b[2][4][4];
     ws_read<LA>(mine, li, h, a[0]);
     ws_read<LA>(mine + WS_SLAB, li, h, a[1]);
@@ -1226,10 +1087,8 @@ __device__ __forceinline__ void wstage64_body(const MesmGemmArgs& p, const Blk b
 #pragma unroll
           for (int j = 0; j < 4; ++j) csum[t] += a[t][s_][j];
     }
-    L64_STAMP(5 + 3 * st);
   }
   asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
-  L64_STAMP(28);
   if (BF == 2 && hs.a.e + hs.b.e != 0) {  // back to unit scale before the waves' partial tiles meet
     const int back = -(hs.a.e + hs.b.e);
 #pragma unroll
@@ -1274,9 +1133,7 @@ __device__ __forceinline__ void wstage64_body(const MesmGemmArgs& p, const Blk b
   __syncthreads();  // dslope_store reuses the head of L
   tile16_epilogue<LA, LB, XF>(p, sum, m0 + 32 * (wave >> 1), n0 + 32 * (wave & 1), slope, seed_off, blk.z, L, blk.slot,
                               KM, xa, xb);
-  L64_STAMP(29);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  L64_STAMP(30);
 }
 
 template <int LA, int LB, bool XF, int BF = 0>
@@ -1326,39 +1183,6 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_wstage64_group_kernel(const 
     else if (sel == 2) wstage64_body<O, R, true, 0>(p, blk, L);
     else wstage64_body<O, O, true, 0>(p, blk, L);
   }
-}
-
-
-// MESM_GEMM_BF16X: 6 = split-bf16 products, three exact terms (see SplitFrag); 2 = two fp16 terms, three products (HalfFrag);
-// anything else = exact f32
-inline bool layout_masks() {  // MESM_G64_LAYOUT_MASKS=0: the four-variant kernel for every grouped 64 x 64 launch (A/B)
-  static const bool v = []() { const char* e = getenv("MESM_G64_LAYOUT_MASKS"); return !(e && atoi(e) == 0); }();
-  return v;
-}
-inline int bf16x_mode() { return mesm_gemm_bf16x(); }
-int mesm_gemm_group64();
-
-
-template <int LA, int LB>
-int launch_wstage64_l(const MesmGemmArgs& a, hipStream_t s) {
-  dim3 grid(((a.M + 63) / 64) * ((a.N + 63) / 64), 1, a.split_k > 1 ? a.split_k : 1);  // 1-D: xcd_tile() maps it
-  const bool xf = a.a_act != MESM_ACT_NONE || a.b_act != MESM_ACT_NONE || a.a_drop_p > 0.f || a.b_drop_p > 0.f;
-  const int bf = xf ? 0 : bf16x_mode();  // (operand transforms + split: 260-288 VGPRs, one workgroup per CU or spills)
-  const SideRed sr = take_side(s);
-  if (bf == 6) hipLaunchKernelGGL((gemm_wstage64_kernel<LA, LB, false, 6>), grid, dim3(NTHREADS), 0, s, a, sr);
-  else if (bf == 2) hipLaunchKernelGGL((gemm_wstage64_kernel<LA, LB, false, 2>), grid, dim3(NTHREADS), 0, s, a, sr);
-  else if (xf) hipLaunchKernelGGL((gemm_wstage64_kernel<LA, LB, true>), grid, dim3(NTHREADS), 0, s, a, sr);
-  else hipLaunchKernelGGL((gemm_wstage64_kernel<LA, LB, false>), grid, dim3(NTHREADS), 0, s, a, sr);
-  const int rc = mesm_launch_status();
-  return rc != MESM_OK ? rc : dslope_finish(a, grid, s);
-}
-
-int launch_wstage64(const MesmGemmArgs& a, hipStream_t s) {
-  constexpr int R = MESM_LAYOUT_REDUCE_CONTIG, O = MESM_LAYOUT_OUTER_CONTIG;
-  if (a.a_layout == R && a.b_layout == R) return launch_wstage64_l<R, R>(a, s);
-  if (a.a_layout == R && a.b_layout == O) return launch_wstage64_l<R, O>(a, s);
-  if (a.a_layout == O && a.b_layout == O) return launch_wstage64_l<O, O>(a, s);
-  return launch_wstage64_l<O, R>(a, s);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1519,25 +1343,6 @@ __global__ __launch_bounds__(NTHREADS) void gemm_wtall_kernel(const MesmGemmArgs
   wtall_body<LA, LB, XF, RB>(p, blk, L);
 }
 
-template <int LA, int LB, int RB>
-int launch_wtall_l(const MesmGemmArgs& a, hipStream_t s) {
-  dim3 grid(((a.M + 32 * RB - 1) / (32 * RB)) * ((a.N + 31) / 32), 1, a.split_k > 1 ? a.split_k : 1);
-  const bool xf = a.a_act != MESM_ACT_NONE || a.b_act != MESM_ACT_NONE || a.a_drop_p > 0.f || a.b_drop_p > 0.f;
-  if (xf) hipLaunchKernelGGL((gemm_wtall_kernel<LA, LB, true, RB>), grid, dim3(NTHREADS), 0, s, a);
-  else hipLaunchKernelGGL((gemm_wtall_kernel<LA, LB, false, RB>), grid, dim3(NTHREADS), 0, s, a);
-  const int rc = mesm_launch_status();
-  return rc != MESM_OK ? rc : dslope_finish(a, grid, s);
-}
-
-template <int RB>
-int launch_wtall(const MesmGemmArgs& a, hipStream_t s) {
-  constexpr int R = MESM_LAYOUT_REDUCE_CONTIG, O = MESM_LAYOUT_OUTER_CONTIG;
-  if (a.a_layout == R && a.b_layout == R) return launch_wtall_l<R, R, RB>(a, s);
-  if (a.a_layout == R && a.b_layout == O) return launch_wtall_l<R, O, RB>(a, s);
-  if (a.a_layout == O && a.b_layout == O) return launch_wtall_l<O, O, RB>(a, s);
-  return launch_wtall_l<O, R, RB>(a, s);
-}
-
 // wtall has no column-sum output (the bias-gradient side product of the weight-gradient GEMMs)
 bool wtall_ok(const MesmGemmArgs& a) { return wstage_ok(a) && a.colsum == nullptr; }
 
@@ -1549,18 +1354,7 @@ bool wtall_ok(const MesmGemmArgs& a) { return wstage_ok(a) && a.colsum == nullpt
 // bookkeeping does not drain the ring before every fragment read (it waits vmcnt(0) on any LDS access
 // that may alias an LDS-DMA it knows about): the only waits on the ring are the counted ones below.
 // Slab layouts / source-address swizzles are the wstage kernel's (ws_issue_asm mirrors ws_issue).
-#ifndef MESM_L64_STAGES
-#define MESM_L64_STAGES 3
-#endif
-#ifndef MESM_L64_WAVES
-#define MESM_L64_WAVES 0
-#endif
-#if MESM_L64_WAVES > 0
-#define L64_BOUNDS __launch_bounds__(NTHREADS, MESM_L64_WAVES)  // second argument = waves per SIMD the register budget must admit
-#else
-#define L64_BOUNDS __launch_bounds__(NTHREADS)
-#endif
-constexpr int L64_STAGES = MESM_L64_STAGES;  // ring depth: STAGES - 1 k-tiles in flight behind the one being multiplied (16 KB each; at most 8)
+constexpr int L64_STAGES = 3;  // ring depth: STAGES - 1 k-tiles in flight behind the one being multiplied (16 KB each; at most 8)
 static_assert(L64_STAGES >= 2 && L64_STAGES <= 8, "ring depth");
 constexpr int L64_STAGE_FLOATS = 4 * WS_SLAB;  // A rows 0-31, A rows 32-63, B rows 0-31, B rows 32-63
 
@@ -1637,19 +1431,14 @@ __device__ __forceinline__ void l64_issue(const float* __restrict__ base, int64_
   }
 }
 
-
-// Tuning builds (tools/build_variant.sh): -DMESM_L64_STAGES / -DMESM_L64_WAVES change ring depth and the
-// occupancy target; -DMESM_L64_NO_LOAD / _NO_MFMA / _NO_STORE are kill switches that remove one phase
-// (wrong results, timing only) -- the decomposition quoted in DESIGN.md section 8 comes from them.
 template <int LA, int LB, bool XF>
-__global__ L64_BOUNDS void gemm_lds64_kernel(const MesmGemmArgs p, const SideRed sr) {
+__global__ __launch_bounds__(NTHREADS) void gemm_lds64_kernel(const MesmGemmArgs p, const SideRed sr) {
   side_reduce(sr);
   __shared__ __attribute__((aligned(16))) float L[L64_STAGES * L64_STAGE_FLOATS];
   const int tid = threadIdx.x;
   const int lane = tid & 63, wave = tid >> 6;
   const int li = lane & 31, h = lane >> 5;
   const int wm = wave >> 1, wn = wave & 1;
-  L64_STAMP(0);
   int tbx, tby, tbz;
   xcd_tile_z((int)linear_block(), (p.M + 63) / 64, (p.N + 63) / 64, p.split_k, tbx, tby, tbz);
   const int m0 = tbx * 64, n0 = tby * 64;
@@ -1688,9 +1477,6 @@ __global__ L64_BOUNDS void gemm_lds64_kernel(const MesmGemmArgs p, const SideRed
   else srcB.init(p.B, p.ldb, n0 + 32 * (wave_u - 2), p.N, kbeg, lane);
   int i_slot = 0;  // ring slot of the next k-tile to issue
   auto issue = [&](int st) {
-#ifdef MESM_L64_NO_LOAD
-    return;
-#endif
     const unsigned slab = L_base + (unsigned)(i_slot * L64_STAGE_FLOATS + wave_u * WS_SLAB) * 4u;
     i_slot = i_slot + 1 == L64_STAGES ? 0 : i_slot + 1;
     const int kb = kbeg + 32 * st;
@@ -1712,11 +1498,9 @@ __global__ L64_BOUNDS void gemm_lds64_kernel(const MesmGemmArgs p, const SideRed
 
   constexpr int AHEAD = L64_STAGES - 1;  // k-tiles in flight behind the one being multiplied
   int c_slot = 0;                        // ring slot of the k-tile being multiplied
-  L64_STAMP(1);
 #pragma unroll
   for (int i = 0; i < AHEAD; ++i)
     if (i < nst) issue(i);
-  L64_STAMP(2);
   for (int st = 0; st < nst; ++st) {
     // this wave's 4 LDS-DMA instructions of k-tile st have landed; the min(AHEAD - 1, nst - 1 - st)
     // k-tiles issued after it may still fly (4 instructions each, returned in issue order) ...
@@ -1732,11 +1516,9 @@ __global__ L64_BOUNDS void gemm_lds64_kernel(const MesmGemmArgs p, const SideRed
         default: asm volatile("s_waitcnt vmcnt(24)" ::: "memory"); break;
       }
     }
-    L64_STAMP(3 + 3 * st);  // this wave's loads of k-tile st landed
     // ... and so have the other waves': one barrier per k-tile.  It also orders the fragment reads of
     // k-tile st-1 (finished by every wave before it arrived here) ahead of the refill issued below.
     __builtin_amdgcn_s_barrier();
-    L64_STAMP(4 + 3 * st);  // every wave's landed
     if (st + AHEAD < nst) issue(st + AHEAD);
     const float* buf = L + c_slot * L64_STAGE_FLOATS;
     c_slot = c_slot + 1 == L64_STAGES ? 0 : c_slot + 1;
@@ -1773,31 +1555,19 @@ __global__ L64_BOUNDS void gemm_lds64_kernel(const MesmGemmArgs p, const SideRed
           b[s_][j] = y;
         }
     }
-#ifdef MESM_L64_NO_MFMA
-#pragma unroll
-    for (int s_ = 0; s_ < 4; ++s_)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) acc[4 * s_ + j] += a[s_][j] * b[s_][j];
-#else
 #pragma unroll
     for (int s_ = 0; s_ < 4; ++s_)
 #pragma unroll
       for (int j = 0; j < 4; ++j)
         acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[s_][j], b[s_][j], acc, 0, 0, 0);
-#endif
     if (do_colsum) {
 #pragma unroll
       for (int s_ = 0; s_ < 4; ++s_)
 #pragma unroll
         for (int j = 0; j < 4; ++j) csum += a[s_][j];
     }
-    L64_STAMP(5 + 3 * st);  // MFMAs of k-tile st issued
   }
   asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
-  L64_STAMP(28);
-#ifdef MESM_L64_NO_STORE
-  if (acc[0] != 12345.678f) return;
-#endif
 
   if (do_colsum) {
     csum = add_xor32(csum);
@@ -1807,43 +1577,7 @@ __global__ L64_BOUNDS void gemm_lds64_kernel(const MesmGemmArgs p, const SideRed
   }
 
   tile16_epilogue<LA, LB, XF>(p, acc, m0 + 32 * wm, n0 + 32 * wn, slope, seed_off, tbz, L, linear_block(), KM, xa, xb);
-  L64_STAMP(29);  // stores issued
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  L64_STAMP(30);  // stores acknowledged
-#ifdef MESM_L64_TRACE
-  {
-    unsigned hw;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-    unsigned xcc;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-    if (threadIdx.x == 0 && blockIdx.x < 1024 && blockIdx.z == 0) l64_trace[blockIdx.x * 32 + 31] = ((unsigned long long)xcc << 32) | hw;
-  }
-#endif
-}
-
-#ifdef MESM_L64_TRACE
-extern "C" int mesm_l64_trace_read(unsigned long long* host) {
-  return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(l64_trace), sizeof(unsigned long long) * 1024 * 32);
-}
-#endif
-
-template <int LA, int LB>
-int launch_lds64_l(const MesmGemmArgs& a, hipStream_t s) {
-  dim3 grid(((a.M + 63) / 64) * ((a.N + 63) / 64), 1, a.split_k > 1 ? a.split_k : 1);  // 1-D: xcd_tile() maps it
-  const bool xf = a.a_act != MESM_ACT_NONE || a.b_act != MESM_ACT_NONE || a.a_drop_p > 0.f || a.b_drop_p > 0.f;
-  const SideRed sr = take_side(s);
-  if (xf) hipLaunchKernelGGL((gemm_lds64_kernel<LA, LB, true>), grid, dim3(NTHREADS), 0, s, a, sr);
-  else hipLaunchKernelGGL((gemm_lds64_kernel<LA, LB, false>), grid, dim3(NTHREADS), 0, s, a, sr);
-  const int rc = mesm_launch_status();
-  return rc != MESM_OK ? rc : dslope_finish(a, grid, s);
-}
-
-int launch_lds64(const MesmGemmArgs& a, hipStream_t s) {
-  constexpr int R = MESM_LAYOUT_REDUCE_CONTIG, O = MESM_LAYOUT_OUTER_CONTIG;
-  if (a.a_layout == R && a.b_layout == R) return launch_lds64_l<R, R>(a, s);
-  if (a.a_layout == R && a.b_layout == O) return launch_lds64_l<R, O>(a, s);
-  if (a.a_layout == O && a.b_layout == O) return launch_lds64_l<O, O>(a, s);
-  return launch_lds64_l<O, R>(a, s);
 }
 
 // Tape of the GEMM launches of one step (argument structs as launched), for bench.py's
@@ -1862,7 +1596,10 @@ struct Tape {
 };
 Tape g_tape;
 
-// tuning switches, read ONCE when the library is loaded (they used to be getenv calls per dispatch)
+// Switches, read ONCE when the library is loaded; mesm_gemm_set_switches changes them between calls (tuning tools, tests).
+// MESM_GEMM_TILE: 0 = the automatic choice; 1 = frag, 2 = wstage (k-split 32 x 32), 3 = lds64 (64 x 64 LDS-DMA ring),
+// 4 = wstage64 (k-split 64 x 64), 6 = wtall (96 x 32), 32 | 64 | 128 = register-staged tile.  A product the forced
+// kernel cannot take falls through to the automatic choice among the register-staged tiles and the kernels below it.
 int g_force_tile = []() { const char* e = getenv("MESM_GEMM_TILE"); return e ? atoi(e) : 0; }();
 // MESM_GEMM_BF16X: 2 (default since round 6) = the large products on v_mfma_f32_32x32x16_f16 over operands split into two
 // fp16 terms under a wave-owned power-of-two scale, THREE cross products, f32 accumulate (gemm_ws.hpp; error at or below the
@@ -1871,54 +1608,340 @@ int g_force_tile = []() { const char* e = getenv("MESM_GEMM_TILE"); return e ? a
 // 0 = every product on v_mfma_f32_32x32x2_f32.  (The two-term bf16 form, 16 significand bits, failed 13 parity tests: deleted.)
 int g_bf16x = []() { const char* e = getenv("MESM_GEMM_BF16X"); const int m = e ? atoi(e) : 2; return (m == 2 || m == 6) ? m : 0; }();
 
-int mesm_gemm_force_tile() { return g_force_tile; }
-int mesm_gemm_bf16x() { return g_bf16x; }
-// MESM_GEMM_GROUP64: 1 = the problems of a grouped call that the 64 x 64 k-split kernel takes share ONE
-// launch, and the call's other products ride along (default in the three-term split-bf16 mode: 4.40 -> 4.01
-// ms/step; in exact-f32 mode it loses, 4.609 -> 4.642, and stays off; off in the experimental two-term mode as well, whose
-// grouped kernel is not instantiated: every product of that mode then runs the two-term split); 0 = launched one by one
-int g_group64 = []() { const char* e = getenv("MESM_GEMM_GROUP64"); return e ? atoi(e) : -1; }();
-int mesm_gemm_group64() { return g_group64 >= 0 ? g_group64 : (g_bf16x != 0 ? 1 : 0); }
+// Questions earlier rounds answered with A/B switches; the answers are constants now.
+// Grouped 64 x 64 launch, split modes only (exact-f32: 4.609 -> 4.642 ms, profiles/r4c/group64_ab.txt): admits >= 128 tiles of
+// 64 x 64 with >= 1024 rows or reduce indices, the tall tile's shapes included, and whatever the 32 x 32 group would take
+// rides along (profiles/r4c/g64_sweeps.txt, r4d/g64_final_sweep.txt; 256 tiles: 3.30 -> 3.71 ms, r6q/ab_knobs_after_write_through.txt)
+constexpr int G64_MIN_B64 = 128;
+constexpr int G64_MIN_DIM = 1024;
+// A kernel costs ~9 us of ramp whatever it computes (profiles/r3c/tile_compare.txt): in an exact-f32 call that has a grouped
+// 32 x 32 launch anyway, the products below MID_FLOPS that the kernel can take join it (profiles/HISTORY.md, round 3)
+constexpr double MID_FLOPS = 1.5e9;
+// Always on: members issued longest reduce slice first (profiles/r5d/dw_split_ab.txt), grouped kernels built for their members'
+// operand layouts (profiles/r6s/ab_layout_masks.txt), slope-gradient partials carried by the next launch (profiles/HISTORY.md).
 
-int dispatch(const MesmGemmArgs& a, int vec, hipStream_t s) {
-  {
-    // small problems (fewer than ~2 workgroups of 64x64 per CU): register-fragment kernel
-    const long z = a.split_k > 1 ? a.split_k : 1;
-    const long b64 = (long)((a.M + 63) / 64) * ((a.N + 63) / 64) * z;
-    const int force = g_force_tile;  // 1 = frag kernel, 32 | 64 | 128 = staged tile, 0 = auto
-    // 1 = frag, 2 = wstage (k-split 32x32, wave-private LDS-DMA), 3 = lds64 (64x64, LDS-DMA ring),
-    // 4 = wstage64 (k-split 64x64),
-    // 32 | 64 | 128 = register-staged tile, 0 = auto
-    // tall 96 x 32 k-split tiles: the 2400-row, 256-wide GEMMs with a long reduce range (2400 x 256 x 2818 input
-    // projections 52 -> 43 us, x 1024 22.3 -> 19.2, x 512 13.4 -> 12.7): 25 x 8 = 200 equal workgroups in one
-    // round instead of 152.  (160 x 32 on the 4800-row GEMMs measured no gain: 14.1 vs 13.2 us at K = 256 --
-    // those are bound by launch + first-load + epilogue latency, not by the second round of tiles.)
-    {
-      const long t96 = (long)((a.M + 95) / 96) * ((a.N + 31) / 32);
-      if ((force == 6 || (force == 0 && z == 1 && a.K >= 512 && t96 >= 160 && t96 <= 256)) && wtall_ok(a))
-        return launch_wtall<3>(a, s);
-    }
-    // experimental split-bf16 mode: the 64 x 64-per-wave kernel is the one that carries it (the split costs VALU per
-    // fragment value, amortised over four products there) -- every problem of >= 2400 output rows or reduce indices
-    // with enough tiles goes there, whatever its round count
-    // (... or >= 512 tiles whatever the extents: the 1024 x 5003 x 256 vocabulary head used to fall through to the
-    // exact-f32 64 x 64 ring, 37 us; the split kernel takes its 1,264 tiles in 28)
-    if (force == 0 && bf16x_mode() != 0 && wstage_ok(a) && b64 >= 128 && (a.M >= 2400 || a.K >= 2400 || b64 >= 512) &&
-        a.a_act == MESM_ACT_NONE && a.b_act == MESM_ACT_NONE && a.a_drop_p == 0.f && a.b_drop_p == 0.f)
-      return launch_wstage64(a, s);
-    if ((force == 3 || (force == 0 && b64 >= 512)) && wstage_ok(a)) return launch_lds64(a, s);
-    // k-split 64 x 64 (half the L2 traffic per flop): wins only when its workgroups fit ONE round on the
-    // 256 CUs (300 workgroups = two rounds: 4800 x 256 x 1024 59 us vs 43 us with 32 x 32 tiles) and a
-    // wave has >= 4 stages to pipeline: the split-K FFN weight gradients and the 2400-row K = 1024 GEMMs
-    const long kper = ((a.K + z - 1) / z + 3) / 4;
-    if ((force == 4 || (force == 0 && b64 >= 128 && b64 <= 256 && kper >= 128)) && wstage_ok(a))
-      return launch_wstage64(a, s);
-    if ((force == 2 || (force == 0 && b64 < 512)) && wstage_ok(a)) return launch_wstage(a, s);
-    if ((force == 1 || (force == 0 && b64 < 512)) && frag_ok(a)) return launch_frag(a, s);
+// ------------------------------------------------------------------------------------------------
+// What a call turns into.  A Route names ONE kernel instantiation up to the operand layouts (which are the problem's own);
+// a Plan holds the launches of a call in issue order and, per problem, the launch it shares.
+enum Family { TILE32 = 0, TILE64, TILE128, FRAG, WSTAGE, WSTAGE64, WTALL, LDS64 };
+
+struct Route {
+  int family = TILE32;
+  int xf = 0;       // XF / XFM: the kernel holds the operand-transform bodies
+  int stages = 0;   // wstage: k-tiles resident per wave
+  int bf = 0;       // wstage64: split arithmetic (0 | 2 | 6)
+  int mask = 0;     // grouped kernels: the operand-layout pairs in the kernel
+  int vec = 0;      // register-staged tiles: global load width
+  int add = 0;      // register-staged tiles, frag: 1 = A2, 2 = B2
+  int grouped = 0;  // the GroupArgs kernel of the family
+  int variant() const { return xf | stages << 1 | bf << 3 | mask << 6 | vec << 10 | add << 13 | grouped << 15; }
+};
+
+struct Launch {
+  Route route;
+  int n = 0;
+  int member[GROUP_MAX];  // positions in the call's (sorted) list
+};
+
+enum Where { ALONE = 0, G32, G64 };
+
+struct Plan {
+  int n_launches = 0;
+  Launch launches[64];
+  int launch_of[64];
+  int where[64];  // what MESM_GEMM_PLAN_LOG prints
+  void issue(Launch& l) {
+    for (int k = 0; k < l.n; ++k) launch_of[l.member[k]] = n_launches;
+    launches[n_launches++] = l;
+    l.n = 0;
   }
-  if (vec == 4) return launch_tile<4>(a, s);
-  if (vec == 2) return launch_tile<2>(a, s);
-  return launch_tile<1>(a, s);
+  void issue_alone(const Route& r, int i) {
+    Launch l;
+    l.route = r;
+    l.member[l.n++] = i;
+    where[i] = ALONE;
+    issue(l);
+  }
+};
+
+// what the rules look at, computed once per problem
+struct Shape {
+  long z;        // k-slices
+  long b64;      // workgroups of 64 x 64 tiles
+  long kper;     // 4-index steps of one k-slice
+  long t96;      // tiles of 96 x 32
+  bool xf;       // operand transforms
+  int add;       // 1 = A2, 2 = B2
+  double flops;
+};
+
+Shape shape_of(const MesmGemmArgs& a) {
+  Shape d;
+  d.z = a.split_k > 1 ? a.split_k : 1;
+  d.b64 = (long)((a.M + 63) / 64) * ((a.N + 63) / 64) * d.z;
+  d.kper = ((a.K + d.z - 1) / d.z + 3) / 4;
+  d.t96 = (long)((a.M + 95) / 96) * ((a.N + 31) / 32);
+  d.xf = has_xform(a);
+  d.add = a.A2 ? 1 : (a.B2 ? 2 : 0);
+  d.flops = 2.0 * a.M * a.N * a.K;
+  return d;
+}
+
+// the template variant of family f for problem a
+Route variant_of(int f, const MesmGemmArgs& a, const Shape& d, int vec) {
+  Route r;
+  r.family = f;
+  if (f <= TILE128) { r.vec = vec; r.add = d.add; return r; }
+  r.xf = d.xf;
+  if (f == FRAG) r.add = d.add;
+  if (f == WSTAGE) r.stages = ws_stages_for(a);
+  if (f == WSTAGE64 && !d.xf) r.bf = g_bf16x;  // (operand transforms + split: 260-288 VGPRs, one workgroup per CU or spills)
+  return r;
+}
+
+// The single-problem rule.  `alone` = false asks for the problem's class as a member of a grouped call: there the tall tile
+// is not an option, and operand transforms do not move a product out of the split modes' large class (what they do
+// is keep it out of the grouped 64 x 64 launch).
+Route route_one(const MesmGemmArgs& a, const Shape& d, int vec, bool alone = true) {
+  const int force = g_force_tile;
+  const bool ws = wstage_ok(a);
+  auto to = [&](int f) { return variant_of(f, a, d, vec); };
+  // tall 96 x 32 k-split tiles: the 2400-row, 256-wide GEMMs with a long reduce range (2400 x 256 x 2818 input
+  // projections 52 -> 43 us, x 1024 22.3 -> 19.2, x 512 13.4 -> 12.7): 25 x 8 = 200 equal workgroups in one
+  // round instead of 152.  (160 x 32 on the 4800-row GEMMs measured no gain: 14.1 vs 13.2 us at K = 256 --
+  // those are bound by launch + first-load + epilogue latency, not by the second round of tiles.)
+  if ((force == 6 || (force == 0 && alone && d.z == 1 && a.K >= 512 && d.t96 >= 160 && d.t96 <= 256)) && wtall_ok(a)) return to(WTALL);
+  // split modes: the 64 x 64-per-wave kernel is the one that carries them (the split costs VALU per fragment value,
+  // amortised over four products there) -- every problem of >= 2400 output rows or reduce indices with enough tiles goes
+  // there, whatever its round count (... or >= 512 tiles whatever the extents: the 1024 x 5003 x 256 vocabulary head used
+  // to fall through to the exact-f32 64 x 64 ring, 37 us; the split kernel takes its 1,264 tiles in 28)
+  if (force == 0 && g_bf16x != 0 && ws && d.b64 >= 128 && (a.M >= 2400 || a.K >= 2400 || d.b64 >= 512) && !(d.xf && alone))
+    return to(WSTAGE64);
+  if ((force == 3 || (force == 0 && d.b64 >= 512)) && ws) return to(LDS64);
+  // k-split 64 x 64 (half the L2 traffic per flop): wins only when its workgroups fit ONE round on the
+  // 256 CUs (300 workgroups = two rounds: 4800 x 256 x 1024 59 us vs 43 us with 32 x 32 tiles) and a
+  // wave has >= 4 stages to pipeline: the split-K FFN weight gradients and the 2400-row K = 1024 GEMMs
+  if ((force == 4 || (force == 0 && d.b64 >= 128 && d.b64 <= 256 && d.kper >= 128)) && ws) return to(WSTAGE64);
+  // small problems (fewer than ~2 workgroups of 64 x 64 per CU): the k-split 32 x 32 kernels
+  if ((force == 2 || (force == 0 && d.b64 < 512)) && ws) return to(WSTAGE);
+  if ((force == 1 || (force == 0 && d.b64 < 512)) && frag_ok(a)) return to(FRAG);
+  // register-staged tiles: MESM_GEMM_TILE = 32 | 64 | 128 pins the tile (128 has no addend form); otherwise the largest
+  // tile that still gives every CU about two workgroups
+  auto blocks = [&](int t) { return (long)((a.M + t - 1) / t) * ((a.N + t - 1) / t) * d.z; };
+  if (force == 128 && d.add == 0) return to(TILE128);
+  if (force == 64) return to(TILE64);
+  if (force == 32) return to(TILE32);
+  if (blocks(128) >= 512 && d.add == 0) return to(TILE128);
+  if (blocks(64) >= 512) return to(TILE64);
+  return to(TILE32);
+}
+
+inline int layout_bit(const MesmGemmArgs& a) {
+  return 1 << ((a.a_layout == MESM_LAYOUT_OUTER_CONTIG ? 2 : 0) + (a.b_layout == MESM_LAYOUT_OUTER_CONTIG ? 1 : 0));
+}
+inline bool mask_built(int mask) { return mask == 1 || mask == 2 || mask == 8 || mask == 10; }  // the layout sets a kernel exists for
+
+// The route of a grouped launch over members l.member[0 .. l.n) of family f (WSTAGE | WSTAGE64); one member runs the
+// family's single-problem kernel.
+Route group_route(int f, const Launch& l, const MesmGemmArgs* list, const Shape* d, const int* vecs) {
+  if (l.n == 1) return variant_of(f, list[l.member[0]], d[l.member[0]], vecs[l.member[0]]);
+  Route r;
+  r.family = f;
+  r.grouped = 1;
+  bool any_xf = false, one = true;  // single-stage staging only if every member wants it
+  for (int k = 0; k < l.n; ++k) {
+    const int i = l.member[k];
+    r.mask |= layout_bit(list[i]);
+    any_xf = any_xf || d[i].xf;
+    one = one && ws_stages_for(list[i]) == 1;
+  }
+  if (f == WSTAGE) {
+    r.stages = one ? 1 : 2;
+    if (any_xf || !one || !mask_built(r.mask)) { r.mask = 15; r.xf = 1; }
+  } else {
+    r.bf = g_bf16x;
+    if (r.bf != 2 || !mask_built(r.mask)) r.mask = 15;
+  }
+  return r;
+}
+
+// The plan of a grouped call over list[0 .. n) (already sorted): problems the k-split 32 x 32 kernel takes go into grouped
+// launches of up to GROUP_MAX, in the split modes the large ones into grouped 64 x 64 launches that the former then ride
+// along with; the rest go alone, at once.  A full launch is issued in the middle of the call, the open ones at its end.
+void plan_group(const MesmGemmArgs* list, const int* vecs, int n, Plan& plan) {
+  Shape d[64];
+  bool in32[64], in64[64];
+  int n32 = 0, n64 = 0;
+  const bool g64_on = g_force_tile == 0 && g_bf16x != 0;
+  for (int i = 0; i < n; ++i) {
+    const MesmGemmArgs& a = list[i];
+    d[i] = shape_of(a);
+    in32[i] = route_one(a, d[i], vecs[i], false).family == WSTAGE;
+    in64[i] = g64_on && wstage_ok(a) && !d[i].xf && d[i].b64 >= G64_MIN_B64 && (a.M >= G64_MIN_DIM || a.K >= G64_MIN_DIM);
+    n32 += in32[i];
+    n64 += in64[i];
+  }
+  const bool mid = g_force_tile == 0 && g_bf16x == 0 && n32 > 0;
+  Launch g32, g64;
+  auto flush = [&](Launch& g, int family) {
+    g.route = group_route(family, g, list, d, vecs);
+    plan.issue(g);
+  };
+  for (int i = 0; i < n; ++i) {
+    const MesmGemmArgs& a = list[i];
+    if (in64[i] || (n64 > 0 && in32[i] && !d[i].xf)) {
+      plan.where[i] = G64;
+      g64.member[g64.n++] = i;
+      if (g64.n == GROUP_MAX) flush(g64, WSTAGE64);
+    } else if (in32[i] || (mid && wstage_ok(a) && d[i].flops < MID_FLOPS)) {
+      plan.where[i] = G32;
+      g32.member[g32.n++] = i;
+      if (g32.n == GROUP_MAX) flush(g32, WSTAGE);
+    } else {
+      plan.issue_alone(route_one(a, d[i], vecs[i]), i);
+    }
+  }
+  if (g32.n) flush(g32, WSTAGE);
+  if (g64.n) flush(g64, WSTAGE64);
+}
+
+// a single call (mesm_gemm_f32) is the single-problem rule; a grouped call of one is not (it may be the 64 x 64 class)
+void make_plan(const MesmGemmArgs* list, const int* vecs, int n, bool grouped, Plan& plan) {
+  if (grouped) return plan_group(list, vecs, n, plan);
+  plan.issue_alone(route_one(list[0], shape_of(list[0]), vecs[0]), 0);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Executing a plan: route -> kernel instantiation -> launch.  The only launches of the GEMM kernels are here.
+template <int V>
+using Int = std::integral_constant<int, V>;
+
+// f(LA, LB) with the operand layouts of a as compile-time constants
+template <class F>
+auto with_layouts(const MesmGemmArgs& a, F&& f) {
+  using R = Int<MESM_LAYOUT_REDUCE_CONTIG>;
+  using O = Int<MESM_LAYOUT_OUTER_CONTIG>;
+  if (a.a_layout == R::value) return a.b_layout == R::value ? f(R{}, R{}) : f(R{}, O{});
+  return a.b_layout == O::value ? f(O{}, O{}) : f(O{}, R{});
+}
+
+using Kernel = void (*)(const MesmGemmArgs);                        // frag, wtall, register-staged tiles
+using KernelSide = void (*)(const MesmGemmArgs, const SideRed);     // wstage, wstage64, lds64: carry pending slope reductions
+using KernelGroup = void (*)(const GroupArgs, const SideRed);
+
+template <int BM, int LA, int LB>
+Kernel tile_kernel(const Route& r) {
+  // 64x64 tiles run few MFMAs per k-step: a deeper k-step (64) keeps the MFMA block longer than
+  // the global-load latency it has to hide; 128x128 tiles already do with 32.
+  constexpr int BK = (BM == 128) ? 32 : 64;
+  auto by_add = [&](auto vec) -> Kernel {
+    constexpr int VEC = decltype(vec)::value;
+    if constexpr (BM == 128) return gemm_f32_kernel<BM, BM, BK, LA, LB, VEC, 0>;
+    else return r.add == 0 ? gemm_f32_kernel<BM, BM, BK, LA, LB, VEC, 0>
+              : r.add == 1 ? gemm_f32_kernel<BM, BM, BK, LA, LB, VEC, 1> : gemm_f32_kernel<BM, BM, BK, LA, LB, VEC, 2>;
+  };
+  return r.vec == 4 ? by_add(Int<4>{}) : r.vec == 2 ? by_add(Int<2>{}) : by_add(Int<1>{});
+}
+
+Kernel plain_kernel(const MesmGemmArgs& a, const Route& r) {
+  return with_layouts(a, [&](auto la, auto lb) -> Kernel {
+    constexpr int LA = decltype(la)::value, LB = decltype(lb)::value;
+    switch (r.family) {
+      case TILE32: return tile_kernel<32, LA, LB>(r);
+      case TILE64: return tile_kernel<64, LA, LB>(r);
+      case TILE128: return tile_kernel<128, LA, LB>(r);
+      case WTALL: return r.xf ? gemm_wtall_kernel<LA, LB, true, 3> : gemm_wtall_kernel<LA, LB, false, 3>;
+      default:  // FRAG
+        if (r.xf) return r.add == 0 ? gemm_frag_kernel<LA, LB, 0, true> : r.add == 1 ? gemm_frag_kernel<LA, LB, 1, true> : gemm_frag_kernel<LA, LB, 2, true>;
+        return r.add == 0 ? gemm_frag_kernel<LA, LB, 0, false> : r.add == 1 ? gemm_frag_kernel<LA, LB, 1, false> : gemm_frag_kernel<LA, LB, 2, false>;
+    }
+  });
+}
+
+KernelSide side_kernel(const MesmGemmArgs& a, const Route& r) {
+  return with_layouts(a, [&](auto la, auto lb) -> KernelSide {
+    constexpr int LA = decltype(la)::value, LB = decltype(lb)::value;
+    switch (r.family) {
+      case WSTAGE:
+        if (r.xf) return r.stages == 1 ? gemm_wstage_kernel<LA, LB, true, 1> : gemm_wstage_kernel<LA, LB, true, 2>;
+        return r.stages == 1 ? gemm_wstage_kernel<LA, LB, false, 1> : gemm_wstage_kernel<LA, LB, false, 2>;
+      case WSTAGE64:
+        if (r.bf == 6) return gemm_wstage64_kernel<LA, LB, false, 6>;
+        if (r.bf == 2) return gemm_wstage64_kernel<LA, LB, false, 2>;
+        return r.xf ? gemm_wstage64_kernel<LA, LB, true> : gemm_wstage64_kernel<LA, LB, false>;
+      default:  // LDS64
+        return r.xf ? gemm_lds64_kernel<LA, LB, true> : gemm_lds64_kernel<LA, LB, false>;
+    }
+  });
+}
+
+KernelGroup group_kernel(const Route& r) {
+  if (r.family == WSTAGE) {
+    if (r.stages == 2) return gemm_wstage_group_kernel<2>;
+    switch (r.mask) {
+      case 1: return gemm_wstage_group_kernel<1, 1, false>;
+      case 2: return gemm_wstage_group_kernel<1, 2, false>;
+      case 8: return gemm_wstage_group_kernel<1, 8, false>;
+      case 10: return gemm_wstage_group_kernel<1, 10, false>;
+      default: return gemm_wstage_group_kernel<1>;
+    }
+  }
+  if (r.bf == 6) return gemm_wstage64_group_kernel<6>;
+  if (r.bf == 0) return gemm_wstage64_group_kernel<0>;  // (no rule routes here since the launch is tied to the split modes)
+  switch (r.mask) {
+    case 1: return gemm_wstage64_group_kernel<2, 1>;
+    case 2: return gemm_wstage64_group_kernel<2, 2>;
+    case 8: return gemm_wstage64_group_kernel<2, 8>;
+    case 10: return gemm_wstage64_group_kernel<2, 10>;
+    default: return gemm_wstage64_group_kernel<2>;
+  }
+}
+
+// output tile of a family's workgroup, by Family; the k-split and LDS-DMA kernels take a 1-D grid that xcd_tile_z() maps
+struct TileDims { int bm, bn; bool flat; };
+constexpr TileDims TILE_DIMS[8] = {{32, 32, false}, {64, 64, false}, {128, 128, false}, {32, 32, false},
+                                   {32, 32, true},  {64, 64, true},  {96, 32, true},    {64, 64, true}};
+
+int execute(const Plan& plan, const MesmGemmArgs* list, hipStream_t s) {
+  for (int li = 0; li < plan.n_launches; ++li) {
+    const Launch& l = plan.launches[li];
+    const Route& r = l.route;
+    const TileDims t = TILE_DIMS[r.family];
+    auto tiles = [&](const MesmGemmArgs& a) { return dim3((a.M + t.bm - 1) / t.bm, (a.N + t.bn - 1) / t.bn, a.split_k > 1 ? a.split_k : 1); };
+    const dim3 threads(r.family == WSTAGE ? WS_THREADS : NTHREADS);
+    int rc;
+    if (r.grouped) {
+      GroupArgs g;
+      g.n = l.n;
+      g.start[0] = 0;
+      for (int k = 0; k < l.n; ++k) {
+        g.p[k] = list[l.member[k]];
+        const dim3 gr = tiles(g.p[k]);
+        g.start[k + 1] = g.start[k] + gr.x * gr.y * gr.z;
+      }
+      const KernelGroup kernel = group_kernel(r);
+      const SideRed sr = take_side(s);
+      hipLaunchKernelGGL(kernel, dim3(g.start[g.n]), threads, 0, s, g, sr);
+      rc = mesm_launch_status();
+      for (int k = 0; k < g.n && rc == MESM_OK; ++k) rc = dslope_finish_n(g.p[k], g.start[k + 1] - g.start[k], s);
+    } else {
+      const MesmGemmArgs& a = list[l.member[0]];
+      dim3 grid = tiles(a);
+      if (t.flat) grid = dim3(grid.x * grid.y, 1, grid.z);
+      if (r.family == WSTAGE || r.family == WSTAGE64 || r.family == LDS64) {
+        const KernelSide kernel = side_kernel(a, r);
+        const SideRed sr = take_side(s);
+        hipLaunchKernelGGL(kernel, grid, threads, 0, s, a, sr);
+      } else {
+        const Kernel kernel = plain_kernel(a, r);
+        hipLaunchKernelGGL(kernel, grid, threads, 0, s, a);
+      }
+      rc = mesm_launch_status();
+      if (rc == MESM_OK) rc = dslope_finish(a, grid, s);
+    }
+    if (rc != MESM_OK) return rc;
+  }
+  return MESM_OK;
 }
 
 // argument validation / normalisation shared by the single and the grouped entry
@@ -1962,216 +1985,93 @@ int prepare(MesmGemmArgs& a, int& vec) {
   return MESM_OK;
 }
 
-// does the auto dispatch send this problem to the wstage kernel (the one that can be grouped)?
-bool groupable(const MesmGemmArgs& a) {
-  const int force = g_force_tile;
-  if (force != 0 && force != 2) return false;
-  {
-    const long b64g = (long)((a.M + 63) / 64) * ((a.N + 63) / 64) * (a.split_k > 1 ? a.split_k : 1);
-    if (force == 0 && bf16x_mode() != 0 && b64g >= 128 && (a.M >= 2400 || a.K >= 2400 || b64g >= 512))
-      return false;  // split mode: goes to the split-bf16 kernel on its own
-  }
-  const long z = a.split_k > 1 ? a.split_k : 1;
-  const long b64 = (long)((a.M + 63) / 64) * ((a.N + 63) / 64) * z;
-  const long kper = ((a.K + z - 1) / z + 3) / 4;
-  if (force == 0 && b64 >= 128 && b64 <= 256 && kper >= 128) return false;  // goes to wstage64
-  return (force == 2 || b64 < 512) && wstage_ok(a);
-}
-
-}  // namespace
-
-extern "C" int mesm_gemm_f32(const MesmGemmArgs* args, void* stream) {
-  if (!args) return MESM_EINVAL;
-  MesmGemmArgs a = *args;
-  int vec = 1;
-  const int rc = prepare(a, vec);
-  if (rc != MESM_OK) return rc;
-  if (g_tape.recording) { TapeEntry e; e.args = {a}; e.vecs = {vec}; g_tape.launches.push_back(e); }
-  return dispatch(a, vec, (hipStream_t)stream);
-}
-
-namespace {
-int launch_group(const MesmGemmArgs* list, const int* vecs, int n, hipStream_t s) {
-  // problems the wstage kernel takes go into grouped launches of up to GROUP_MAX; the rest go alone
-  GroupArgs g;
-  g.n = 0;
-  g.start[0] = 0;
-  int rc = MESM_OK;
-  auto flush = [&]() {
-    if (g.n == 0) return;
-    if (g.n == 1) {
-      rc = launch_wstage(g.p[0], s);
-    } else {
-      bool one = true;  // single-stage staging only if every problem of the group wants it
-      for (int k = 0; k < g.n; ++k) one = one && ws_stages_for(g.p[k]) == 1;
-      const SideRed sr = take_side(s);
-      constexpr int O_ = MESM_LAYOUT_OUTER_CONTIG;
-      int mask = 0;
-      bool any_xf = false;
-      for (int k = 0; k < g.n; ++k) {
-        const MesmGemmArgs& a = g.p[k];
-        mask |= 1 << ((a.a_layout == O_ ? 2 : 0) + (a.b_layout == O_ ? 1 : 0));
-        any_xf = any_xf || a.a_act != MESM_ACT_NONE || a.b_act != MESM_ACT_NONE || a.a_drop_p > 0.f || a.b_drop_p > 0.f;
-      }
-      if (!layout_masks() || any_xf || !one) mask = 15;
-      const dim3 gr(g.start[g.n]), bl(WS_THREADS);
-      if (one && mask == 1) hipLaunchKernelGGL((gemm_wstage_group_kernel<1, 1, false>), gr, bl, 0, s, g, sr);
-      else if (one && mask == 2) hipLaunchKernelGGL((gemm_wstage_group_kernel<1, 2, false>), gr, bl, 0, s, g, sr);
-      else if (one && mask == 8) hipLaunchKernelGGL((gemm_wstage_group_kernel<1, 8, false>), gr, bl, 0, s, g, sr);
-      else if (one && mask == 10) hipLaunchKernelGGL((gemm_wstage_group_kernel<1, 10, false>), gr, bl, 0, s, g, sr);
-      else if (one) hipLaunchKernelGGL(gemm_wstage_group_kernel<1>, gr, bl, 0, s, g, sr);
-      else hipLaunchKernelGGL(gemm_wstage_group_kernel<2>, gr, bl, 0, s, g, sr);
-      rc = mesm_launch_status();
-      for (int k = 0; k < g.n && rc == MESM_OK; ++k) {
-        const MesmGemmArgs& a = g.p[k];
-        dim3 grid((a.M + 31) / 32, (a.N + 31) / 32, a.split_k > 1 ? a.split_k : 1);
-        rc = dslope_finish(a, grid, s);
-      }
-    }
-    g.n = 0;
-  };
-  // A kernel costs ~9 us of ramp whatever it computes (profiles/r3c/tile_compare.txt), more than a specialised tile
-  // saves on a mid-size product (the tall 96 x 32 tile on 2400 x 256 x 512: 13.4 -> 12.7 us alone): in a call that has a
-  // grouped launch anyway, the products below MID_GF that the 32 x 32 kernel can take join it instead of getting a
-  // kernel of their own.  MESM_GEMM_GROUP_MID=0: the standalone rule only (A/B).
-  static const bool group_mid = []() { const char* e = getenv("MESM_GEMM_GROUP_MID"); return !(e && atoi(e) == 0); }();
-  constexpr double MID_GF = 1.5e9;
-  int n_plain = 0;
-  for (int i = 0; i < n; ++i) n_plain += groupable(list[i]) ? 1 : 0;
-  auto joins = [&](const MesmGemmArgs& a) {
-    if (groupable(a)) return true;
-    if (!group_mid || n_plain == 0 || bf16x_mode() != 0) return false;
-    if (g_force_tile != 0) return false;
-    return wstage_ok(a) && 2.0 * a.M * a.N * a.K < MID_GF;
-  };
-  // 64 x 64 class: what the single dispatch would hand to the k-split 64 x 64 kernel
-  GroupArgs g64;
-  g64.n = 0;
-  g64.start[0] = 0;
-  auto flush64 = [&]() {
-    if (g64.n == 0) return;
-    if (g64.n == 1) {
-      rc = launch_wstage64(g64.p[0], s);
-    } else {
-      const SideRed sr = take_side(s);
-      const int bf = bf16x_mode();
-      constexpr int O_ = MESM_LAYOUT_OUTER_CONTIG;
-      int mask = 0;  // the operand-layout pairs of this launch's members (see the kernel)
-      for (int k = 0; k < g64.n; ++k) mask |= 1 << ((g64.p[k].a_layout == O_ ? 2 : 0) + (g64.p[k].b_layout == O_ ? 1 : 0));
-      if (!layout_masks()) mask = 15;
-      const dim3 gr(g64.start[g64.n]);
-      if (bf == 6) hipLaunchKernelGGL(gemm_wstage64_group_kernel<6>, gr, dim3(NTHREADS), 0, s, g64, sr);
-      else if (bf == 2 && mask == 1) hipLaunchKernelGGL((gemm_wstage64_group_kernel<2, 1>), gr, dim3(NTHREADS), 0, s, g64, sr);
-      else if (bf == 2 && mask == 2) hipLaunchKernelGGL((gemm_wstage64_group_kernel<2, 2>), gr, dim3(NTHREADS), 0, s, g64, sr);
-      else if (bf == 2 && mask == 8) hipLaunchKernelGGL((gemm_wstage64_group_kernel<2, 8>), gr, dim3(NTHREADS), 0, s, g64, sr);
-      else if (bf == 2 && mask == 10) hipLaunchKernelGGL((gemm_wstage64_group_kernel<2, 10>), gr, dim3(NTHREADS), 0, s, g64, sr);
-      else if (bf == 2) hipLaunchKernelGGL(gemm_wstage64_group_kernel<2>, dim3(g64.start[g64.n]), dim3(NTHREADS), 0, s, g64, sr);
-      else hipLaunchKernelGGL(gemm_wstage64_group_kernel<0>, dim3(g64.start[g64.n]), dim3(NTHREADS), 0, s, g64, sr);
-      rc = mesm_launch_status();
-      for (int k = 0; k < g64.n && rc == MESM_OK; ++k) {
-        const MesmGemmArgs& a = g64.p[k];
-        rc = dslope_finish_n(a, (int64_t)((a.M + 63) / 64) * ((a.N + 63) / 64) * (a.split_k > 1 ? a.split_k : 1), s);
-      }
-    }
-    g64.n = 0;
-  };
-  auto joins64 = [&](const MesmGemmArgs& a) {
-    if (mesm_gemm_group64() == 0 || g_force_tile != 0 || !wstage_ok(a)) return false;
-    const long z = a.split_k > 1 ? a.split_k : 1;
-    const long b64 = (long)((a.M + 63) / 64) * ((a.N + 63) / 64) * z;
-    const long kper = ((a.K + z - 1) / z + 3) / 4;
-    const long t96 = (long)((a.M + 95) / 96) * ((a.N + 31) / 32);
-    static const int min_dim = []() { const char* e = getenv("MESM_G64_MINDIM"); return e ? atoi(e) : 1024; }();
-    static const int min_b64 = []() { const char* e = getenv("MESM_G64_MINB64"); return e ? atoi(e) : 128; }();
-    static const int tall = []() { const char* e = getenv("MESM_G64_TALL"); return e ? atoi(e) : 1; }();
-    if (!tall && z == 1 && a.K >= 512 && t96 >= 160 && t96 <= 256 && wtall_ok(a)) return false;  // the tall tile's shapes
-    const bool xf = a.a_act != MESM_ACT_NONE || a.b_act != MESM_ACT_NONE || a.a_drop_p > 0.f || a.b_drop_p > 0.f;
-    if (bf16x_mode() != 0) return !xf && b64 >= min_b64 && (a.M >= min_dim || a.K >= min_dim);
-    return b64 >= 128 && b64 <= 256 && kper >= 128;
-  };
-  // a call that has a 64 x 64 launch anyway: products of >= join_mf MFLOP that the 32 x 32 group would take ride along
-  static const double join_mf = []() { const char* e = getenv("MESM_G64_JOIN_MF"); return e ? atof(e) : 0.0; }();
-  int n64 = 0;
-  for (int i = 0; i < n; ++i) n64 += joins64(list[i]) ? 1 : 0;
-  auto rides64 = [&](const MesmGemmArgs& a) {
-    if (n64 == 0 || join_mf < 0.0 || mesm_gemm_group64() == 0 || !joins(a)) return false;
-    const bool xf = a.a_act != MESM_ACT_NONE || a.b_act != MESM_ACT_NONE || a.a_drop_p > 0.f || a.b_drop_p > 0.f;
-    if (xf && bf16x_mode() != 0) return false;
-    return 2.0 * a.M * a.N * a.K >= join_mf * 1e6;
-  };
-  for (int i = 0; i < n && rc == MESM_OK; ++i) {
-    const MesmGemmArgs& a = list[i];
-    if (joins64(a) || rides64(a)) {
-      const int wgs = ((a.M + 63) / 64) * ((a.N + 63) / 64) * (a.split_k > 1 ? a.split_k : 1);
-      g64.p[g64.n] = a;
-      g64.start[g64.n + 1] = g64.start[g64.n] + wgs;
-      if (++g64.n == GROUP_MAX) flush64();
-    } else if (joins(a)) {
-      const int wgs = ((a.M + 31) / 32) * ((a.N + 31) / 32) * (a.split_k > 1 ? a.split_k : 1);
-      g.p[g.n] = a;
-      g.start[g.n + 1] = g.start[g.n] + wgs;
-      if (++g.n == GROUP_MAX) flush();
-    } else {
-      rc = dispatch(a, vecs[i], s);
-    }
-  }
-  if (rc == MESM_OK) flush();
-  if (rc == MESM_OK) flush64();
-  static const bool plan_log = getenv("MESM_GEMM_PLAN_LOG") != nullptr;  // tools/gemm_plan.py: what a call turned into
-  if (plan_log) {
-    fprintf(stderr, "[gemm plan] call of %d:", n);
-    for (int i = 0; i < n; ++i) {
-      const MesmGemmArgs& a = list[i];
-      const bool xf = a.a_act != MESM_ACT_NONE || a.b_act != MESM_ACT_NONE || a.a_drop_p > 0.f || a.b_drop_p > 0.f;
-      const char* where = (joins64(a) || rides64(a)) ? "g64" : (joins(a) ? "g32" : "alone");
-      fprintf(stderr, " %dx%dx%d%s%s/s%d%s%s->%s", a.M, a.N, a.K, a.a_layout == MESM_LAYOUT_OUTER_CONTIG ? "T" : "N",
-              a.b_layout == MESM_LAYOUT_REDUCE_CONTIG ? "T" : "N", a.split_k, xf ? "(xf)" : "", (a.A2 || a.B2) ? "(2nd)" : "", where);
-    }
-    fprintf(stderr, "\n");
-  }
-  return rc;
-}
-}  // namespace
-
-extern "C" int mesm_gemm_group(const MesmGemmArgs* args, int32_t n, void* stream) {
-  if (!args || n <= 0 || n > 64) return MESM_EINVAL;
-  MesmGemmArgs list[64];
-  int vecs[64];
+// prepare every problem of a call and sort them, longest tiles first: the members of a call are independent, a
+// workgroup's time is its slice of the reduce range, and the hardware hands out workgroups in index order -- a long-K member
+// (a split-K weight gradient: 19 stages per wave) behind short ones (dX at K = 256: 1-2 stages) would start its tiles last
+// and end the launch alone.  order[i] = the call's index of the problem at position i.
+int prepare_call(const MesmGemmArgs* args, int n, MesmGemmArgs* list, int* vecs, int* order) {
+  MesmGemmArgs in[64];
+  int vin[64];
   for (int i = 0; i < n; ++i) {
-    list[i] = args[i];
-    const int rc = prepare(list[i], vecs[i]);
+    in[i] = args[i];
+    order[i] = i;
+    const int rc = prepare(in[i], vin[i]);
     if (rc != MESM_OK) return rc;
   }
-  // longest tiles first: the members of a call are independent, a workgroup's time is its slice of the reduce range, and
-  // the hardware hands out workgroups in index order -- a long-K member (a split-K weight gradient: 19 stages per wave)
-  // behind short ones (dX at K = 256: 1-2 stages) would start its tiles last and end the launch alone
-  static const bool lpt = [] { const char* e = getenv("MESM_GEMM_LPT"); return !e || atoi(e) != 0; }();
-  if (lpt && n > 1) {
-    int order[64];
-    for (int i = 0; i < n; ++i) order[i] = i;
-    auto depth = [&](int i) { return (list[i].K + list[i].split_k - 1) / list[i].split_k; };
-    std::stable_sort(order, order + n, [&](int a, int b) { return depth(a) > depth(b); });
-    MesmGemmArgs l2[64];
-    int v2[64];
-    for (int i = 0; i < n; ++i) { l2[i] = list[order[i]]; v2[i] = vecs[order[i]]; }
-    for (int i = 0; i < n; ++i) { list[i] = l2[i]; vecs[i] = v2[i]; }
+  auto depth = [&](int i) { return (in[i].K + in[i].split_k - 1) / in[i].split_k; };
+  std::stable_sort(order, order + n, [&](int a, int b) { return depth(a) > depth(b); });
+  for (int i = 0; i < n; ++i) { list[i] = in[order[i]]; vecs[i] = vin[order[i]]; }
+  return MESM_OK;
+}
+
+// tools/gemm_plan.py: what a grouped call turned into
+void log_plan(const Plan& plan, const MesmGemmArgs* list, int n) {
+  static const char* const where[] = {"alone", "g32", "g64"};
+  fprintf(stderr, "[gemm plan] call of %d:", n);
+  for (int i = 0; i < n; ++i) {
+    const MesmGemmArgs& a = list[i];
+    fprintf(stderr, " %dx%dx%d%s%s/s%d%s%s->%s", a.M, a.N, a.K, a.a_layout == MESM_LAYOUT_OUTER_CONTIG ? "T" : "N",
+            a.b_layout == MESM_LAYOUT_REDUCE_CONTIG ? "T" : "N", a.split_k, has_xform(a) ? "(xf)" : "", (a.A2 || a.B2) ? "(2nd)" : "",
+            where[plan.where[i]]);
   }
+  fprintf(stderr, "\n");
+}
+
+// plan + execute of prepared problems (the entries below and the tape's replays)
+int run(const MesmGemmArgs* list, const int* vecs, int n, bool grouped, hipStream_t s) {
+  static const bool plan_log = getenv("MESM_GEMM_PLAN_LOG") != nullptr;
+  Plan plan;
+  make_plan(list, vecs, n, grouped, plan);
+  const int rc = execute(plan, list, s);
+  if (plan_log && grouped) log_plan(plan, list, n);
+  return rc;
+}
+
+int call(const MesmGemmArgs* args, int n, bool grouped, hipStream_t s) {
+  if (!args || n <= 0 || n > 64) return MESM_EINVAL;
+  MesmGemmArgs list[64];
+  int vecs[64], order[64];
+  const int rc = prepare_call(args, n, list, vecs, order);
+  if (rc != MESM_OK) return rc;
   if (g_tape.recording) {
     TapeEntry e;
     e.args.assign(list, list + n);
     e.vecs.assign(vecs, vecs + n);
-    e.group = 1;
+    e.group = grouped;
     e.n = n;
     g_tape.launches.push_back(e);
   }
-  return launch_group(list, vecs, n, (hipStream_t)stream);
+  return run(list, vecs, n, grouped, s);
+}
+
+}  // namespace
+
+extern "C" int mesm_gemm_f32(const MesmGemmArgs* args, void* stream) { return call(args, 1, false, (hipStream_t)stream); }
+extern "C" int mesm_gemm_group(const MesmGemmArgs* args, int32_t n, void* stream) { return call(args, n, true, (hipStream_t)stream); }
+
+extern "C" int mesm_gemm_plan(const MesmGemmArgs* args, int32_t n, int32_t* out) {
+  const int count = n > 0 ? n : 1;
+  if (!args || !out || n < 0 || n > 64) return MESM_EINVAL;
+  MesmGemmArgs list[64];
+  int vecs[64], order[64];
+  const int rc = prepare_call(args, count, list, vecs, order);
+  if (rc != MESM_OK) return rc;
+  Plan plan;
+  make_plan(list, vecs, count, n > 0, plan);
+  for (int pos = 0; pos < count; ++pos) {
+    const Route& r = plan.launches[plan.launch_of[pos]].route;
+    int32_t* o = out + 4 * order[pos];
+    o[0] = pos; o[1] = r.family; o[2] = r.variant(); o[3] = plan.launch_of[pos];
+  }
+  return MESM_OK;
 }
 
 int mesm_gemm_dslope_finish(const MesmGemmArgs& a, int64_t nblocks, hipStream_t s) { return dslope_finish_n(a, nblocks, s); }
 
-// tuning tools flip the two dispatch switches between calls of one process (< 0: keep)
 extern "C" int mesm_gemm_get_bf16x(void) { return g_bf16x; }
+extern "C" int mesm_gemm_get_force_tile(void) { return g_force_tile; }
 
+// tuning tools and tests flip the two switches between calls of one process (< 0: keep)
 extern "C" int mesm_gemm_set_switches(int32_t force_tile, int32_t bf16x) {
   if (force_tile >= 0) g_force_tile = force_tile;
   if (bf16x >= 0) g_bf16x = (bf16x == 2 || bf16x == 6) ? bf16x : 0;
@@ -2206,7 +2106,7 @@ extern "C" int mesm_gemm_tape_replay(void* stream, int32_t reps, double* total_m
     hipEventRecord(e0, s);
     for (size_t i = 0; i < n && rc == MESM_OK; ++i) {
       const TapeEntry& e = g_tape.launches[i];
-      rc = e.group ? launch_group(e.args.data(), e.vecs.data(), e.n, s) : dispatch(e.args[0], e.vecs[0], s);
+      rc = run(e.args.data(), e.vecs.data(), e.n, e.group != 0, s);
     }
     if (rc == MESM_OK) rc = flush_side(s);
     hipEventRecord(e1, s);
@@ -2263,7 +2163,7 @@ extern "C" int mesm_gemm_tape_entry(void* stream, int32_t idx, int32_t reps, dou
   int rc = MESM_OK;
   hipEventRecord(e0, s);
   for (int r = 0; r < reps && rc == MESM_OK; ++r)
-    rc = e.group ? launch_group(e.args.data(), e.vecs.data(), e.n, s) : dispatch(e.args[0], e.vecs[0], s);
+    rc = run(e.args.data(), e.vecs.data(), e.n, e.group != 0, s);
   if (rc == MESM_OK) rc = flush_side(s);
   hipEventRecord(e1, s);
   hipStreamSynchronize(s);
@@ -2276,7 +2176,7 @@ extern "C" int mesm_gemm_tape_entry(void* stream, int32_t idx, int32_t reps, dou
   for (size_t k = 0; k < e.args.size() && k < 64; ++k) {
     const MesmGemmArgs& a = e.args[k];
     shapes[4 * k] = a.M; shapes[4 * k + 1] = a.N; shapes[4 * k + 2] = a.K;
-    shapes[4 * k + 3] = (a.split_k > 1 ? a.split_k : 1) | (a.a_layout << 8) | (a.b_layout << 9) | (groupable(a) ? 1 << 10 : 0);
+    shapes[4 * k + 3] = (a.split_k > 1 ? a.split_k : 1) | (a.a_layout << 8) | (a.b_layout << 9) | (route_one(a, shape_of(a), e.vecs[k], false).family == WSTAGE ? 1 << 10 : 0);
   }
   return rc;
 }

@@ -95,6 +95,11 @@ __device__ __forceinline__ void dslope_store(const MesmGemmArgs& p, float part, 
 
 inline bool aligned_to(const void* p, size_t b) { return p == nullptr || ((uintptr_t)p % b) == 0; }
 
+// does the product transform an operand on its way in (activation or dropout on A or B)?  (host side: the routing rules)
+inline bool has_xform(const MesmGemmArgs& p) {
+  return p.a_act != MESM_ACT_NONE || p.b_act != MESM_ACT_NONE || p.a_drop_p > 0.f || p.b_drop_p > 0.f;
+}
+
 // Reduce indices [gemm_kmain, K) are NOT staged by the LDS-DMA kernels (wstage / wstage64 / lds64):
 //  * a reduce-contiguous operand is staged in 16-byte chunks along k: the main loop ends at K & ~3;
 //  * an outer-contiguous operand whose outer extent is not a multiple of 4 has one chunk per reduce row
@@ -146,7 +151,7 @@ __device__ __forceinline__ void tail_accumulate(const MesmGemmArgs& p, float (&t
 // register array -- scale+bias, activation, dropout, activation-gradient, residual / read-modify-write,
 // store -- so that every run-time flag of MesmGemmArgs is tested once per wave, not once per element, and
 // the side loads of a stage are all in flight together; row addresses are one per-lane 64-bit base plus
-// wave-uniform multiples of the leading dimension.  (In-kernel stamps, tools/l64_trace.py: the
+// wave-uniform multiples of the leading dimension.  (Measured with in-kernel time stamps in round 3: the
 // per-element form took ~8,000 cycles per 32x32 tile, as long as 3.5 k-tiles of MFMA work.)
 // FULL: the wave's 32 x 32 tile lies inside C, no bounds handling at all.
 template <int NV, bool FULL, typename RowOff>

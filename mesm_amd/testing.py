@@ -1,7 +1,8 @@
 """Hooks that exist for the test suite only; nothing in the product imports this module."""
 import contextlib
 
-from . import ops
+from . import kernels, ops
+from ._lib import lib
 
 
 @contextlib.contextmanager
@@ -14,3 +15,16 @@ def no_relu():
         yield
     finally:
         ops._NO_RELU = False
+
+
+@contextlib.contextmanager
+def gemm_forced(tile):
+    """MESM_GEMM_TILE = tile while the context is open (the library reads the variable once, when it is loaded, so setting
+    it in a running process selects nothing): every GEMM launch goes to that kernel, or, where the kernel cannot take it,
+    falls through to the automatic choice.  The value that was in force comes back on exit."""
+    before = int(lib().mesm_gemm_get_force_tile())
+    kernels.gemm_switches(tile=tile)
+    try:
+        yield
+    finally:
+        kernels.gemm_switches(tile=before)

@@ -148,34 +148,35 @@ def test_gemm_dropout_matches_materialised_mask():
 
 @pytest.mark.parametrize("tile", ["0", "1", "2", "3", "4", "6", "32", "64"])
 @pytest.mark.parametrize("M,N,K", [(2400, 256, 256), (190, 132, 300), (130, 70, 262), (66, 129, 35)])
-def test_gemm_operand_dropout_uses_the_stored_index(tile, M, N, K, monkeypatch):
+def test_gemm_operand_dropout_uses_the_stored_index(tile, M, N, K):
     """The mask an epilogue wrote on Y (index row*N + col) is replayed when dY is an operand:
     as A of dX = drop(dY) @ W and as A^T of dW = drop(dY)^T @ X (+ the bias column sums)."""
     from mesm_amd import kernels as kn
-    monkeypatch.setenv("MESM_GEMM_TILE", tile)
-    dY = gen((M, N), 40)
-    W = gen((N, K), 41)
-    X = gen((M, K), 42)
-    dYd = kn.dropout(dY, 0.1, 1234)
-    dX = torch.empty(M, K, device=dev())
-    kn.gemm(dY, W, dX, a_drop=(0.1, 1234))
-    assert rel_err(dX, dYd.double() @ W.double()) < TOL
-    dW = torch.zeros(N, K, device=dev())
-    db = torch.zeros(N, device=dev())
-    kn.gemm(dY, X, dW, trans_a=True, a_drop=(0.1, 1234), colsum=db, split_k=4, accumulate=2)
-    assert rel_err(dW, dYd.t().double() @ X.double()) < TOL
-    assert rel_err(db, dYd.double().sum(0)) < TOL
-    # and operand B stored (N, K) (trans_b): index n*K + k
-    Wd = kn.dropout(W, 0.1, 99)
-    C = torch.empty(M, N, device=dev())
-    kn.gemm(X, W, C, trans_b=True, b_drop=(0.1, 99))
-    assert rel_err(C, X.double() @ Wd.t().double()) < TOL
-    # prelu + dropout on A together
-    slope = torch.tensor([0.1], device=dev())
-    Z = gen((M, K), 21)
-    Hd = kn.dropout(torch.where(Z > 0, Z, 0.1 * Z).contiguous(), 0.1, 5)
-    kn.gemm(Z, W, C, trans_b=True, a_act=kn.ACT_PRELU, slope=slope, a_drop=(0.1, 5))
-    assert rel_err(C, Hd.double() @ W.t().double()) < TOL
+    from mesm_amd.testing import gemm_forced
+    with gemm_forced(int(tile)):  # (the library reads MESM_GEMM_TILE once, at load: the environment selects nothing here)
+        dY = gen((M, N), 40)
+        W = gen((N, K), 41)
+        X = gen((M, K), 42)
+        dYd = kn.dropout(dY, 0.1, 1234)
+        dX = torch.empty(M, K, device=dev())
+        kn.gemm(dY, W, dX, a_drop=(0.1, 1234))
+        assert rel_err(dX, dYd.double() @ W.double()) < TOL
+        dW = torch.zeros(N, K, device=dev())
+        db = torch.zeros(N, device=dev())
+        kn.gemm(dY, X, dW, trans_a=True, a_drop=(0.1, 1234), colsum=db, split_k=4, accumulate=2)
+        assert rel_err(dW, dYd.t().double() @ X.double()) < TOL
+        assert rel_err(db, dYd.double().sum(0)) < TOL
+        # and operand B stored (N, K) (trans_b): index n*K + k
+        Wd = kn.dropout(W, 0.1, 99)
+        C = torch.empty(M, N, device=dev())
+        kn.gemm(X, W, C, trans_b=True, b_drop=(0.1, 99))
+        assert rel_err(C, X.double() @ Wd.t().double()) < TOL
+        # prelu + dropout on A together
+        slope = torch.tensor([0.1], device=dev())
+        Z = gen((M, K), 21)
+        Hd = kn.dropout(torch.where(Z > 0, Z, 0.1 * Z).contiguous(), 0.1, 5)
+        kn.gemm(Z, W, C, trans_b=True, a_act=kn.ACT_PRELU, slope=slope, a_drop=(0.1, 5))
+        assert rel_err(C, Hd.double() @ W.t().double()) < TOL
 
 
 # --------------------------------------------------------------------------- LayerNorm
@@ -817,69 +818,72 @@ def test_gemm_group_matches_individual_launches():
 
 
 @pytest.mark.parametrize("tile", ["0", "2", "3", "4", "6"])
-def test_gemm_reference_widths_on_the_lds_dma_kernels(tile, monkeypatch):
+def test_gemm_reference_widths_on_the_lds_dma_kernels(tile):
     """Dv = 2818 and the 5003-word vocabulary: rows 8- / 4-byte aligned, K % 4 = 2 / 3, outer extents that
     are not multiples of 4 -- forward, input-gradient and weight-gradient forms, plus strided views."""
     from mesm_amd import kernels as kn
-    monkeypatch.setenv("MESM_GEMM_TILE", tile)
-    for (rows, wide, d) in [(300, 2818, 256), (200, 5003, 64)]:
-        X = gen((rows, wide), 1); W = gen((d, wide), 2, 0.1); b = gen((d,), 3)
-        Y = torch.empty(rows, d, device=dev())
-        kn.gemm(X, W, Y, trans_b=True, bias=b, e_act=kn.ACT_RELU)                       # K = wide
-        assert rel_err(Y, (X.double() @ W.double().t() + b.double()).clamp(min=0)) < TOL
-        dY = gen((rows, d), 4)
-        dX = torch.empty(rows, wide, device=dev())
-        kn.gemm(dY, W, dX)                                                               # N = wide (outer-contiguous B)
-        assert rel_err(dX, dY.double() @ W.double()) < TOL
-        dW = torch.zeros(d, wide, device=dev()); db = torch.zeros(d, device=dev())
-        kn.gemm(dY, X, dW, trans_a=True, colsum=db, split_k=4, accumulate=2)             # dW = dY^T X
-        assert rel_err(dW, dY.double().t() @ X.double()) < TOL
-        assert rel_err(db, dY.double().sum(0)) < TOL
-        dWt = torch.zeros(wide, d, device=dev()); dbt = torch.zeros(wide, device=dev())
-        kn.gemm(X, dY, dWt, trans_a=True, colsum=dbt, split_k=2, accumulate=2)           # M = wide (outer-contiguous A)
-        assert rel_err(dWt, X.double().t() @ dY.double()) < TOL
-        assert rel_err(dbt, X.double().sum(0)) < TOL
-        Xv = X[:, 1:wide - 2]                                                            # odd start, K = wide - 3
-        kn.gemm(Xv, W[:, 1:wide - 2], Y, trans_b=True)
-        assert rel_err(Y, Xv.double() @ W[:, 1:wide - 2].double().t()) < TOL
+    from mesm_amd.testing import gemm_forced
+    with gemm_forced(int(tile)):  # (the library reads MESM_GEMM_TILE once, at load: the environment selects nothing here)
+        for (rows, wide, d) in [(300, 2818, 256), (200, 5003, 64)]:
+            X = gen((rows, wide), 1); W = gen((d, wide), 2, 0.1); b = gen((d,), 3)
+            Y = torch.empty(rows, d, device=dev())
+            kn.gemm(X, W, Y, trans_b=True, bias=b, e_act=kn.ACT_RELU)                       # K = wide
+            assert rel_err(Y, (X.double() @ W.double().t() + b.double()).clamp(min=0)) < TOL
+            dY = gen((rows, d), 4)
+            dX = torch.empty(rows, wide, device=dev())
+            kn.gemm(dY, W, dX)                                                               # N = wide (outer-contiguous B)
+            assert rel_err(dX, dY.double() @ W.double()) < TOL
+            dW = torch.zeros(d, wide, device=dev()); db = torch.zeros(d, device=dev())
+            kn.gemm(dY, X, dW, trans_a=True, colsum=db, split_k=4, accumulate=2)             # dW = dY^T X
+            assert rel_err(dW, dY.double().t() @ X.double()) < TOL
+            assert rel_err(db, dY.double().sum(0)) < TOL
+            dWt = torch.zeros(wide, d, device=dev()); dbt = torch.zeros(wide, device=dev())
+            kn.gemm(X, dY, dWt, trans_a=True, colsum=dbt, split_k=2, accumulate=2)           # M = wide (outer-contiguous A)
+            assert rel_err(dWt, X.double().t() @ dY.double()) < TOL
+            assert rel_err(dbt, X.double().sum(0)) < TOL
+            Xv = X[:, 1:wide - 2]                                                            # odd start, K = wide - 3
+            kn.gemm(Xv, W[:, 1:wide - 2], Y, trans_b=True)
+            assert rel_err(Y, Xv.double() @ W[:, 1:wide - 2].double().t()) < TOL
 
 
 @pytest.mark.parametrize("tile", ["0", "2", "3", "4", "6"])
-def test_gemm_tiny_reduce_ranges_on_the_lds_dma_kernels(tile, monkeypatch):
+def test_gemm_tiny_reduce_ranges_on_the_lds_dma_kernels(tile):
     """K of 4..9 with outer extents that are not multiples of 4: the MFMA loop may be EMPTY (gemm_kmain = 0)
     and everything comes from the scalar tail, alone or split over k-slices, with bias column sums."""
     from mesm_amd import kernels as kn
-    monkeypatch.setenv("MESM_GEMM_TILE", tile)
-    seed = 0
-    for K in (4, 5, 6, 7, 9):
-        for (M, N) in ((33, 130), (66, 67), (130, 34)):
-            for ta in (False, True):
-                for tb in (False, True):
-                    seed += 1
-                    A = gen((K, M) if ta else (M, K), seed)
-                    B = gen((N, K) if tb else (K, N), seed + 1000)
-                    ref = (A.t() if ta else A).double() @ (B.t() if tb else B).double()
-                    C = torch.empty(M, N, device=dev())
-                    kn.gemm(A, B, C, trans_a=ta, trans_b=tb)
-                    assert rel_err(C, ref) < TOL, (K, M, N, ta, tb)
-                    C2 = torch.zeros(M, N, device=dev()); cs = torch.zeros(M, device=dev())
-                    kn.gemm(A, B, C2, trans_a=ta, trans_b=tb, split_k=2, accumulate=2, colsum=cs)
-                    assert rel_err(C2, ref) < TOL, (K, M, N, ta, tb, "split")
-                    assert rel_err(cs, (A.t() if ta else A).double().sum(1)) < TOL, (K, M, N, ta, tb, "colsum")
+    from mesm_amd.testing import gemm_forced
+    with gemm_forced(int(tile)):  # (the library reads MESM_GEMM_TILE once, at load: the environment selects nothing here)
+        seed = 0
+        for K in (4, 5, 6, 7, 9):
+            for (M, N) in ((33, 130), (66, 67), (130, 34)):
+                for ta in (False, True):
+                    for tb in (False, True):
+                        seed += 1
+                        A = gen((K, M) if ta else (M, K), seed)
+                        B = gen((N, K) if tb else (K, N), seed + 1000)
+                        ref = (A.t() if ta else A).double() @ (B.t() if tb else B).double()
+                        C = torch.empty(M, N, device=dev())
+                        kn.gemm(A, B, C, trans_a=ta, trans_b=tb)
+                        assert rel_err(C, ref) < TOL, (K, M, N, ta, tb)
+                        C2 = torch.zeros(M, N, device=dev()); cs = torch.zeros(M, device=dev())
+                        kn.gemm(A, B, C2, trans_a=ta, trans_b=tb, split_k=2, accumulate=2, colsum=cs)
+                        assert rel_err(C2, ref) < TOL, (K, M, N, ta, tb, "split")
+                        assert rel_err(cs, (A.t() if ta else A).double().sum(1)) < TOL, (K, M, N, ta, tb, "colsum")
 
 
 @pytest.mark.parametrize("tile", ["1", "2", "3", "4", "6"])
-def test_gemm_fuzz_forced_kernel(tile, monkeypatch):
+def test_gemm_fuzz_forced_kernel(tile):
     """The same fuzz with every launch forced onto one of the small-problem / LDS-DMA kernels
     (1 = register fragments, 2 = wave-private LDS-DMA k-split, 3 = 64x64 LDS-DMA ring, 4 = 64x64 k-split,
     6 = tall 96x32 k-split); launches a
     kernel cannot take (addend operands, unaligned rows) fall through to the auto dispatch."""
     import random
     from mesm_amd import kernels as kn
-    monkeypatch.setenv("MESM_GEMM_TILE", tile)
-    rng = random.Random(4321 + int(tile))
-    for _ in range(150):
-        _gemm_fuzz_case(rng, kn)
+    from mesm_amd.testing import gemm_forced
+    with gemm_forced(int(tile)):  # (the library reads MESM_GEMM_TILE once, at load: the environment selects nothing here)
+        rng = random.Random(4321 + int(tile))
+        for _ in range(150):
+            _gemm_fuzz_case(rng, kn)
 
 
 def test_gemm_fuzz_activations():
