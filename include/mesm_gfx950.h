@@ -864,6 +864,19 @@ int mesm_fill_ranges(void* const* ptrs, const int64_t* nbytes, int32_t n, void* 
  * the step).  slot_bytes % 16 == 0; one workgroup. */
 int mesm_step_begin(const void* host_ring, int32_t slot_bytes, int32_t slots, void* dst, int32_t* pull_ctr,
                     int32_t* seed_ctr, void* stream);
+/* Micro-batched graph replays (no counterpart in the reference: k replays of a captured step accumulate into the flat
+ * gradient buffer and ONE optimizer update follows them; every decision is taken on the device).  The cycle state is four
+ * int32 words in device memory, one set per model: state[0] = count (position of the NEXT replay in its cycle, in
+ * [0, k)), state[1] = k (>= 1, written by the host between cycles), state[2] = phase and state[3] = due of the CURRENT
+ * replay.
+ *   mesm_micro_begin        first node of such a graph, one thread: phase = count % k, due = (phase == k - 1),
+ *                           count = (phase + 1) % k, and, when given, *seed_ctr += 1 (the dropout seed offset of the
+ *                           step).  The ONLY writer of the four words on the device.
+ *   mesm_fill_ranges_gated  mesm_fill_ranges iff *phase == 0 (the same write-through 16-byte stores); otherwise every
+ *                           workgroup leaves after one scalar load and no byte is written.  Same checks, plus
+ *                           MESM_EINVAL for a null or misaligned phase. */
+int mesm_micro_begin(int32_t* state, int32_t* seed_ctr, void* stream);
+int mesm_fill_ranges_gated(void* const* ptrs, const int64_t* nbytes, int32_t n, const int32_t* phase, void* stream);
 int mesm_skinny_linear_bwd(const float* dz, const float* x, const float* w, float* dx, float* dw, float* db,
                            int64_t M, int32_t K, int32_t J, int32_t relu_mask, void* stream);
 
@@ -946,6 +959,20 @@ int mesm_adamw_step(float* p, const float* g, float* m, float* v, const uint8_t*
 int mesm_adamw_step_groups(float* p, const float* g, float* m, float* v, const uint8_t* tag4, int64_t n,
                            const float* partials, int32_t np, float max_norm, const MesmAdamGroup* groups,
                            int32_t n_groups, const int32_t* step, float* norm_out, void* stream);
+/* The same three launches behind the `due` word of a micro-step cycle (mesm_micro_begin), for an optimizer tail that
+ * is captured in the step graph: with *due != 0 they are the ungated entries bit for bit (the same kernels, one template
+ * parameter apart); with *due == 0 they write nothing -- not partials, *step, *norm_out, p, m or v.  *np_out is set on
+ * the host either way.  MESM_EINVAL also for a null or misaligned due. */
+int mesm_grad_sumsq_gated(const float* g, int64_t n, float* partials, int32_t* np_out, int32_t* step,
+                          const int32_t* due, void* stream);
+int mesm_adamw_step_gated(float* p, const float* g, float* m, float* v, const uint8_t* active4, int64_t n,
+                          const float* partials, int32_t np, float max_norm, const float* lr, float beta1,
+                          float beta2, float eps, float weight_decay, const int32_t* step, float* norm_out,
+                          const int32_t* due, void* stream);
+int mesm_adamw_step_groups_gated(float* p, const float* g, float* m, float* v, const uint8_t* tag4, int64_t n,
+                                 const float* partials, int32_t np, float max_norm, const MesmAdamGroup* groups,
+                                 int32_t n_groups, const int32_t* step, float* norm_out, const int32_t* due,
+                                 void* stream);
 
 /* ------------------------------------------------------------------------- */
 /*

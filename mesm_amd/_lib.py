@@ -250,6 +250,13 @@ PROTOTYPES = {
     "mesm_weighted_sum": (ctypes.c_int, [c_ptr, c_ptr, _i32, c_ptr, c_ptr]),
     "mesm_scale_vec": (ctypes.c_int, [c_ptr, c_ptr, _i32, c_ptr, c_ptr]),
     "mesm_fill_ranges": (ctypes.c_int, [c_ptr, c_ptr, _i32, c_ptr]),
+    "mesm_fill_ranges_gated": (ctypes.c_int, [c_ptr, c_ptr, _i32, c_ptr, c_ptr]),
+    "mesm_micro_begin": (ctypes.c_int, [c_ptr, c_ptr, c_ptr]),
+    "mesm_grad_sumsq_gated": (ctypes.c_int, [c_ptr, _i64, c_ptr, ctypes.POINTER(ctypes.c_int32), c_ptr, c_ptr, c_ptr]),
+    "mesm_adamw_step_gated": (ctypes.c_int, [c_ptr] * 5 + [_i64, c_ptr, _i32, _f32, c_ptr, _f32, _f32, _f32, _f32,
+                                             c_ptr, c_ptr, c_ptr, c_ptr]),
+    "mesm_adamw_step_groups_gated": (ctypes.c_int, [c_ptr] * 5 + [_i64, c_ptr, _i32, _f32, c_ptr, _i32, c_ptr, c_ptr,
+                                                    c_ptr, c_ptr]),
     "mesm_glue_group": (ctypes.c_int, [ctypes.POINTER(GlueArgs), _i32, c_ptr]),
     "mesm_criterion_fwd": (ctypes.c_int, [ctypes.POINTER(CritFwdArgs), c_ptr]),
     "mesm_criterion_bwd": (ctypes.c_int, [ctypes.POINTER(CritBwdArgs), c_ptr]),

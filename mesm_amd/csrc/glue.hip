@@ -518,7 +518,7 @@ struct FillRanges {
   uint4* p[FILL_MAX];
   int64_t n16[FILL_MAX];
 };
-__global__ __launch_bounds__(256) void fill_ranges_kernel(const FillRanges r) {
+__device__ __forceinline__ void fill_ranges_body(const FillRanges& r) {
   uint4* d = r.p[0];
   int64_t n = r.n16[0];
 #pragma unroll
@@ -526,6 +526,31 @@ __global__ __launch_bounds__(256) void fill_ranges_kernel(const FillRanges r) {
     if ((int)blockIdx.y == k) { d = r.p[k]; n = r.n16[k]; }
   const uint4 z = make_uint4(0u, 0u, 0u, 0u);
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) mesm_store_wt16(d + i, z);
+}
+__global__ __launch_bounds__(256) void fill_ranges_kernel(const FillRanges r) { fill_ranges_body(r); }
+
+// The same fill behind a device gate: the clear of the flat gradient buffer in a micro-stepped graph (graphed.py), which
+// happens on the first replay of a cycle only.  `phase` is written by micro_begin_kernel alone, one node earlier in the
+// graph; here every workgroup reads it (one scalar load) and leaves when it is not 0.
+__global__ __launch_bounds__(256) void fill_ranges_gated_kernel(const FillRanges r, const int32_t* __restrict__ phase) {
+  if (phase[0] != 0) return;
+  fill_ranges_body(r);
+}
+
+// First node of a micro-stepped graph, ONE thread: the cycle state of the model (gradbuf.CycleState), four words
+// {count, k, phase, due}.  phase = count % k is this replay's position in its cycle, due = (phase == k - 1) says that the
+// captured optimizer tail runs; count moves on to the next position (it stays inside [0, k): nothing overflows), and the
+// dropout seed offset of the step advances like the plain graph's counter.add_(1).  This kernel is the only writer of the
+// four words; everything else in the graph reads phase / due.  The host rewrites k (and count, reset_cycle) between
+// cycles only.
+__global__ void micro_begin_kernel(int32_t* __restrict__ st, int32_t* __restrict__ seed_ctr) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  const int32_t k = st[1] > 1 ? st[1] : 1;
+  const int32_t phase = ((st[0] % k) + k) % k;
+  st[2] = phase;
+  st[3] = phase == k - 1 ? 1 : 0;
+  st[0] = phase + 1 == k ? 0 : phase + 1;
+  if (seed_ctr) *seed_ctr += 1;
 }
 
 // First node of a captured step: the step's host draws come from a ring of `slots` buffers in PINNED HOST memory
@@ -764,9 +789,9 @@ extern "C" int mesm_glue_group(const MesmGlueArgs* list, int32_t n, void* stream
   return rc;
 }
 
-extern "C" int mesm_fill_ranges(void* const* ptrs, const int64_t* nbytes, int32_t n, void* stream) {
+// checks and the launch geometry of both fills: the grid's x extent, or a (negative) status
+static int fill_ranges_pack(void* const* ptrs, const int64_t* nbytes, int32_t n, FillRanges& r) {
   if (!ptrs || !nbytes || n <= 0 || n > FILL_MAX) return MESM_EINVAL;
-  FillRanges r = {};
   int64_t most = 0;
   for (int k = 0; k < n; ++k) {
     if (!ptrs[k] || nbytes[k] <= 0 || (nbytes[k] & 15)) return MESM_EINVAL;
@@ -777,6 +802,30 @@ extern "C" int mesm_fill_ranges(void* const* ptrs, const int64_t* nbytes, int32_
   }
   int64_t gx = (most + 255) / 256;
   if (gx > 1024) gx = 1024;
+  return (int)gx;
+}
+
+extern "C" int mesm_fill_ranges(void* const* ptrs, const int64_t* nbytes, int32_t n, void* stream) {
+  FillRanges r = {};
+  const int gx = fill_ranges_pack(ptrs, nbytes, n, r);
+  if (gx < 0) return gx;
   hipLaunchKernelGGL(fill_ranges_kernel, dim3((unsigned)gx, (unsigned)n), dim3(256), 0, (hipStream_t)stream, r);
+  return mesm_launch_status();
+}
+
+extern "C" int mesm_fill_ranges_gated(void* const* ptrs, const int64_t* nbytes, int32_t n, const int32_t* phase,
+                                      void* stream) {
+  if (!phase || ((uintptr_t)phase & 3)) return MESM_EINVAL;
+  FillRanges r = {};
+  const int gx = fill_ranges_pack(ptrs, nbytes, n, r);
+  if (gx < 0) return gx;
+  hipLaunchKernelGGL(fill_ranges_gated_kernel, dim3((unsigned)gx, (unsigned)n), dim3(256), 0, (hipStream_t)stream, r,
+                     phase);
+  return mesm_launch_status();
+}
+
+extern "C" int mesm_micro_begin(int32_t* state, int32_t* seed_ctr, void* stream) {
+  if (!state || ((uintptr_t)state & 3) || ((uintptr_t)seed_ctr & 3)) return MESM_EINVAL;
+  hipLaunchKernelGGL(micro_begin_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, state, seed_ctr);
   return mesm_launch_status();
 }

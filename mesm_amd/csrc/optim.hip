@@ -9,11 +9,21 @@ namespace {
 
 constexpr int OPT_THREADS = 256;
 
+// GATED instantiations (the *_gated entries: the optimizer tail captured in a micro-stepped graph, graphed.py) take one
+// more device word, the cycle's `due` flag, which mesm_micro_begin alone writes: when it is 0 every workgroup leaves after
+// one scalar load, before it has written anything -- partials, the step counter, norm_out, p, m, v.  The ungated
+// instantiations never look at the argument.
+
 // partial sums of squares of the flat gradient buffer, one per workgroup (plain stores);
 // workgroup 0 also advances the device-side step counter
+template <bool GATED>
 __global__ __launch_bounds__(OPT_THREADS) void sumsq_kernel(const float* __restrict__ g, int64_t n4,
                                                            float* __restrict__ partials,
-                                                           int32_t* __restrict__ step) {
+                                                           int32_t* __restrict__ step,
+                                                           const int32_t* __restrict__ due) {
+  if constexpr (GATED) {
+    if (due[0] == 0) return;
+  }
   __shared__ float sh[OPT_THREADS / 64];
   float a = 0.0f;
   for (int64_t i = (int64_t)blockIdx.x * OPT_THREADS + threadIdx.x; i < n4; i += (int64_t)gridDim.x * OPT_THREADS) {
@@ -58,11 +68,15 @@ __global__ __launch_bounds__(OPT_THREADS) void clip_scale_kernel(float* __restri
 
 // AdamW on groups of 4 elements; active4[i] == 0 skips group i (parameters that have no gradient this
 // step are left untouched, exactly like torch.optim skips p.grad is None: no decay, no state update)
+template <bool GATED>
 __global__ __launch_bounds__(OPT_THREADS) void adamw_kernel(
     float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
     const uint8_t* __restrict__ active4, int64_t n4, const float* __restrict__ partials, int np,
     float max_norm, const float* __restrict__ lr_p, float beta1, float beta2, float eps, float wd,
-    const int32_t* __restrict__ step, float* __restrict__ norm_out) {
+    const int32_t* __restrict__ step, float* __restrict__ norm_out, const int32_t* __restrict__ due) {
+  if constexpr (GATED) {
+    if (due[0] == 0) return;
+  }
   __shared__ float sh[OPT_THREADS / 64];
   float coef = 1.0f;
   if (max_norm > 0.0f) {
@@ -110,11 +124,15 @@ struct alignas(16) GroupConsts {
 // once per workgroup from the device table, with adamw_kernel's float expressions (one group over the whole buffer gives
 // adamw_kernel's bits), and kept in LDS; the per-element work is adamw_kernel's plus that indexed read, which is
 // wave-uniform except where two tensors of different groups meet inside a wave.
+template <bool GATED>
 __global__ __launch_bounds__(OPT_THREADS) void adamw_groups_kernel(
     float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
     const uint8_t* __restrict__ tag4, int64_t n4, const float* __restrict__ partials, int np, float max_norm,
     const MesmAdamGroup* __restrict__ groups, int n_groups, const int32_t* __restrict__ step,
-    float* __restrict__ norm_out) {
+    float* __restrict__ norm_out, const int32_t* __restrict__ due) {
+  if constexpr (GATED) {
+    if (due[0] == 0) return;
+  }
   __shared__ float sh[OPT_THREADS / 64];
   __shared__ GroupConsts gc[MESM_ADAM_MAX_GROUPS];
   __shared__ uint32_t live[MESM_ADAM_MAX_GROUPS];  // 0: a group that has not seen a step yet (t < 1) is skipped
@@ -178,15 +196,56 @@ inline int opt_blocks(int64_t n4) {
   return (int)b;
 }
 
+template <bool GATED>
+int grad_sumsq(const float* g, int64_t n, float* partials, int32_t* np_out, int32_t* step, const int32_t* due,
+               void* stream) {
+  if (!g || !partials || !np_out || n <= 0 || (n & 3) || ((uintptr_t)g & 15)) return MESM_EINVAL;
+  if (GATED && (!due || ((uintptr_t)due & 3))) return MESM_EINVAL;
+  const int nb = opt_blocks(n / 4);
+  *np_out = nb;
+  hipLaunchKernelGGL(sumsq_kernel<GATED>, dim3(nb), dim3(OPT_THREADS), 0, (hipStream_t)stream, g, n / 4, partials, step,
+                     due);
+  return mesm_launch_status();
+}
+
+template <bool GATED>
+int adamw_step(float* p, const float* g, float* m, float* v, const uint8_t* active4, int64_t n, const float* partials,
+               int32_t np, float max_norm, const float* lr, float beta1, float beta2, float eps, float weight_decay,
+               const int32_t* step, float* norm_out, const int32_t* due, void* stream) {
+  if (!p || !g || !m || !v || !lr || !step || n <= 0 || (n & 3)) return MESM_EINVAL;
+  if (GATED && (!due || ((uintptr_t)due & 3))) return MESM_EINVAL;
+  if (max_norm > 0.f && (!partials || np <= 0 || np > 1024)) return MESM_EINVAL;
+  if ((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) != 0) return MESM_EALIGN;
+  hipLaunchKernelGGL(adamw_kernel<GATED>, dim3(opt_blocks(n / 4)), dim3(OPT_THREADS), 0, (hipStream_t)stream, p, g, m,
+                     v, active4, n / 4, partials, np, max_norm, lr, beta1, beta2, eps, weight_decay, step, norm_out, due);
+  return mesm_launch_status();
+}
+
+template <bool GATED>
+int adamw_step_groups(float* p, const float* g, float* m, float* v, const uint8_t* tag4, int64_t n,
+                      const float* partials, int32_t np, float max_norm, const MesmAdamGroup* groups, int32_t n_groups,
+                      const int32_t* step, float* norm_out, const int32_t* due, void* stream) {
+  if (!p || !g || !m || !v || !tag4 || !groups || !step || n <= 0 || (n & 3)) return MESM_EINVAL;
+  if (GATED && (!due || ((uintptr_t)due & 3))) return MESM_EINVAL;
+  if (n_groups < 1 || n_groups > MESM_ADAM_MAX_GROUPS) return MESM_EINVAL;
+  if (max_norm > 0.f && (!partials || np <= 0 || np > 1024)) return MESM_EINVAL;
+  if ((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) != 0) return MESM_EALIGN;
+  if (((uintptr_t)groups & 3) != 0) return MESM_EALIGN;
+  hipLaunchKernelGGL(adamw_groups_kernel<GATED>, dim3(opt_blocks(n / 4)), dim3(OPT_THREADS), 0, (hipStream_t)stream, p,
+                     g, m, v, tag4, n / 4, partials, np, max_norm, groups, n_groups, step, norm_out, due);
+  return mesm_launch_status();
+}
+
 }  // namespace
 
 extern "C" int mesm_grad_sumsq(const float* g, int64_t n, float* partials, int32_t* np_out, int32_t* step,
                                void* stream) {
-  if (!g || !partials || !np_out || n <= 0 || (n & 3) || ((uintptr_t)g & 15)) return MESM_EINVAL;
-  const int nb = opt_blocks(n / 4);
-  *np_out = nb;
-  hipLaunchKernelGGL(sumsq_kernel, dim3(nb), dim3(OPT_THREADS), 0, (hipStream_t)stream, g, n / 4, partials, step);
-  return mesm_launch_status();
+  return grad_sumsq<false>(g, n, partials, np_out, step, nullptr, stream);
+}
+
+extern "C" int mesm_grad_sumsq_gated(const float* g, int64_t n, float* partials, int32_t* np_out, int32_t* step,
+                                     const int32_t* due, void* stream) {
+  return grad_sumsq<true>(g, n, partials, np_out, step, due, stream);
 }
 
 extern "C" int mesm_clip_grad(float* g, int64_t n, const float* partials, int32_t np, float max_norm,
@@ -201,24 +260,30 @@ extern "C" int mesm_adamw_step(float* p, const float* g, float* m, float* v, con
                                const float* partials, int32_t np, float max_norm, const float* lr,
                                float beta1, float beta2, float eps, float weight_decay, const int32_t* step,
                                float* norm_out, void* stream) {
-  if (!p || !g || !m || !v || !lr || !step || n <= 0 || (n & 3)) return MESM_EINVAL;
-  if (max_norm > 0.f && (!partials || np <= 0 || np > 1024)) return MESM_EINVAL;
-  if ((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) != 0) return MESM_EALIGN;
-  hipLaunchKernelGGL(adamw_kernel, dim3(opt_blocks(n / 4)), dim3(OPT_THREADS), 0, (hipStream_t)stream, p, g, m, v,
-                     active4, n / 4, partials, np, max_norm, lr, beta1, beta2, eps, weight_decay, step, norm_out);
-  return mesm_launch_status();
+  return adamw_step<false>(p, g, m, v, active4, n, partials, np, max_norm, lr, beta1, beta2, eps, weight_decay, step,
+                           norm_out, nullptr, stream);
+}
+
+extern "C" int mesm_adamw_step_gated(float* p, const float* g, float* m, float* v, const uint8_t* active4, int64_t n,
+                                     const float* partials, int32_t np, float max_norm, const float* lr,
+                                     float beta1, float beta2, float eps, float weight_decay, const int32_t* step,
+                                     float* norm_out, const int32_t* due, void* stream) {
+  return adamw_step<true>(p, g, m, v, active4, n, partials, np, max_norm, lr, beta1, beta2, eps, weight_decay, step,
+                          norm_out, due, stream);
 }
 
 extern "C" int mesm_adamw_step_groups(float* p, const float* g, float* m, float* v, const uint8_t* tag4, int64_t n,
                                       const float* partials, int32_t np, float max_norm,
                                       const MesmAdamGroup* groups, int32_t n_groups, const int32_t* step,
                                       float* norm_out, void* stream) {
-  if (!p || !g || !m || !v || !tag4 || !groups || !step || n <= 0 || (n & 3)) return MESM_EINVAL;
-  if (n_groups < 1 || n_groups > MESM_ADAM_MAX_GROUPS) return MESM_EINVAL;
-  if (max_norm > 0.f && (!partials || np <= 0 || np > 1024)) return MESM_EINVAL;
-  if ((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) != 0) return MESM_EALIGN;
-  if (((uintptr_t)groups & 3) != 0) return MESM_EALIGN;
-  hipLaunchKernelGGL(adamw_groups_kernel, dim3(opt_blocks(n / 4)), dim3(OPT_THREADS), 0, (hipStream_t)stream, p, g, m,
-                     v, tag4, n / 4, partials, np, max_norm, groups, n_groups, step, norm_out);
-  return mesm_launch_status();
+  return adamw_step_groups<false>(p, g, m, v, tag4, n, partials, np, max_norm, groups, n_groups, step, norm_out,
+                                  nullptr, stream);
+}
+
+extern "C" int mesm_adamw_step_groups_gated(float* p, const float* g, float* m, float* v, const uint8_t* tag4,
+                                            int64_t n, const float* partials, int32_t np, float max_norm,
+                                            const MesmAdamGroup* groups, int32_t n_groups, const int32_t* step,
+                                            float* norm_out, const int32_t* due, void* stream) {
+  return adamw_step_groups<true>(p, g, m, v, tag4, n, partials, np, max_norm, groups, n_groups, step, norm_out, due,
+                                 stream);
 }

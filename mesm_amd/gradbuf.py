@@ -58,6 +58,62 @@ class Pack:
         return self.gb.flat[self.offset:self.offset + self.numel].view(self.shape)
 
 
+class CycleState:
+    """Where a model stands in a cycle of micro-batched graph replays (graphed.GraphedStep(micro_steps=k)): four int32 words
+    of DEVICE memory, {count, k, phase, due} (include/mesm_gfx950.h, mesm_micro_begin), that every micro-stepped graph of
+    the model shares -- the micro-batches of one cycle may replay different buckets' graphs -- plus what goes with them:
+    `seed`, the 1 / k the captured backward is seeded with (a tensor, so that k changes without a new capture),
+    and the host's own count of the replays (`pos`, `due`, `updates`), which needs no read-back.  On the device the first
+    node of each graph is the only writer of the words; the host writes k and count between cycles only."""
+    COUNT, K, PHASE, DUE = range(4)
+
+    def __init__(self, device):
+        self.words = torch.zeros(4, dtype=torch.int32, device=device)
+        self.seed = torch.ones(1, dtype=torch.float32, device=device)
+        self.k = 1
+        self.words[self.K:self.K + 1].fill_(1)
+        self.pos = 0          # replays done in the current cycle
+        self.due = False      # the last replay was the k-th of its cycle
+        self.updates = 0      # cycles completed by graphs that carry the optimizer tail
+        self.covered = None   # per parameter: some micro-stepped graph of this model writes its gradient
+
+    @property
+    def phase_word(self):
+        return self.words[self.PHASE:self.PHASE + 1]
+
+    @property
+    def due_word(self):
+        return self.words[self.DUE:self.DUE + 1]
+
+    def set_k(self, k):
+        k = int(k)
+        if k < 1:
+            raise ValueError("micro_steps must be >= 1, got %d" % k)
+        if k == self.k:
+            return
+        if self.pos != 0:
+            raise RuntimeError("micro_steps changes at a cycle boundary only: %d of %d micro-steps of this cycle are "
+                               "done (reset_cycle() drops them)" % (self.pos, self.k))
+        self.k = k
+        self.words[self.K:self.K + 1].fill_(k)
+        self.seed.fill_(1.0 / k)
+
+    def reset(self):
+        """drop an unfinished cycle: the next replay is a first one (it clears the gradient buffer)"""
+        self.words[self.COUNT:self.COUNT + 1].zero_()
+        self.pos, self.due = 0, False
+
+    def advance(self, with_update):
+        """the host's mirror of mesm_micro_begin, after a replay has been launched"""
+        self.pos += 1
+        self.due = self.pos == self.k
+        if self.due:
+            self.pos = 0
+            if with_update:
+                self.updates += 1
+        return self.due
+
+
 class GradBuffer:
     def __init__(self, named_params, packs=None):
         """packs: {key: [parameter names]} -- members are placed back to back (in the given order) in the
@@ -90,6 +146,8 @@ class GradBuffer:
         self.flat = None
         self.pending = False
         self.on_ready = None  # optional callback(param) used by ddp.GradReducer
+        self.cycle = None     # CycleState of micro-batched graph replays; None until a graph asks for it (cycle_state)
+        self.gated = None     # the CycleState while a micro-stepped step body runs: the clear is gated, _adopt adds
         for p in self.params:
             p._mesm_gb = self
             # gradients that reach a parameter through plain autograd (tokens, embeddings used by
@@ -105,7 +163,10 @@ class GradBuffer:
         p.grad = None  # let _open() see the pre-backward state of this parameter
         if self.pending:
             self._open()
-        v.copy_(g)  # (overwrites the whole view: no zero fill in front of it)
+        if self.gated is not None:
+            v.add_(g)  # (a micro-step after the first of its cycle: the view holds the earlier micro-batches' sum)
+        else:
+            v.copy_(g)  # (overwrites the whole view: no zero fill in front of it)
         p.grad = v
         if self.on_ready is not None:
             self.on_ready(p)
@@ -119,13 +180,24 @@ class GradBuffer:
             if p.grad is not None:
                 p.grad = None
 
+    def cycle_state(self, device):
+        """the model's CycleState, made on first use (a model that never micro-steps holds none)"""
+        self.ensure(device)
+        if self.cycle is None or self.cycle.words.device != self.flat.device:
+            self.cycle = CycleState(self.flat.device)
+        return self.cycle
+
     def begin_step(self):
         self.pending = True
 
     def _open(self):
         self.pending = False
         if all(p.grad is None for p in self.params):
-            _zero(self.flat)
+            if self.gated is not None:
+                from . import kernels as kn
+                kn.fill_zero_gated(self.flat, self.gated.phase_word)  # (cleared on the first replay of a cycle only)
+            else:
+                _zero(self.flat)
         else:
             for p in self.params:
                 if p.grad is None:

@@ -138,11 +138,19 @@ class GraphedStep:
     _targets = True  # the arena holds the criterion's target plan
 
     def __init__(self, model, criterion, batch, dataset_name, warmup=3, instrument=False, reducer=None,
-                 caps=None, group_cap=None):
+                 caps=None, group_cap=None, micro_steps=None, optimizer=None, grad_clip=0.0):
         """caps: None = exact extents of `batch` (benchmarks); "auto" = bucketed capacities so that other
-        batches of the same (N, Lv, Lw, groups) replay; or a dict with any of Lc / Lss / T / Tmax."""
+        batches of the same (N, Lv, Lw, groups) replay; or a dict with any of Lc / Lss / T / Tmax.
+        micro_steps=k: k consecutive replays (of this graph or of other micro-stepped graphs of the model) form one cycle
+        whose gradient is the MEAN of the k micro-batch gradients -- what k data-parallel ranks reduce to: the graph clears
+        the flat gradient buffer on the first replay of a cycle only and seeds its backward with 1 / k; `update_due` is
+        True after the k-th.  optimizer= (a FlatAdamW over this model; needs micro_steps, k = 1 allowed) also captures
+        clip + AdamW update behind the backward; they act on the last replay of a cycle only (micro-batched steps)."""
         from .arena import Arena
         from .hostplan import HostSpec
+        self._cycle = None
+        self.optimizer, self.grad_clip = optimizer, float(grad_clip or 0.0)
+        self._check_micro_args(model, reducer, micro_steps, optimizer)
         self.model, self.crit = model, criterion
         self.dataset_name = dataset_name
         self.spec = HostSpec.from_model(model, criterion, dataset_name)
@@ -177,6 +185,8 @@ class GraphedStep:
         # suggested), so the plain copy stays the default.
         self._pull = (_DrawRing(self.arena, self.DRAWN, dev)
                       if dev.type == "cuda" and os.environ.get("MESM_STEP_PULL", "0") == "1" else None)
+        if micro_steps is not None:
+            self._pull = None  # (a micro-stepped graph has its own first node: the draws travel as the plain copy)
         v = self.arena.views
         self.plan = model.plan_from({k[2:]: t for k, t in v.items() if k.startswith("p.")}, self._pmeta)
         self.tplan = None
@@ -192,6 +202,13 @@ class GraphedStep:
             self.batch["_n_valid"] = v["p.n_valid"]
         gb = model.gradbuf()
         gb.ensure(dev)
+        saved_state = None
+        if micro_steps is not None:
+            self._cycle = gb.cycle_state(dev)
+            self._cycle.set_k(micro_steps)
+            # the warm-up steps and the capture run real backward passes (and updates): what a cycle under way has
+            # accumulated, the cycle words, the parameters and the optimizer state come out of them unchanged
+            saved_state = self._save_training_state()
         kn.set_seed_offset(self.counter)
         try:
             side = capture_stream(dev)
@@ -212,6 +229,8 @@ class GraphedStep:
                 with torch.cuda.stream(side):
                     for _ in range(max(warmup, 2 if (reducer is not None and not learnt) else 1)):
                         self._step_body()
+                        if self._cycle is not None:
+                            self._tail()
             finally:
                 gb.on_ready = saved_hook
             torch.cuda.current_stream().wait_stream(side)
@@ -240,16 +259,126 @@ class GraphedStep:
             kn.set_seed_offset(None)
             if instrument:
                 kn.gemm_tape(False)
+            if saved_state is not None:
+                self._restore_training_state(saved_state)
         self._ptrs = self._param_ptrs()
 
     def _capture(self, side):
         """the whole step -- forward, criterion, backward -- as ONE graph (SplitGraphedStep: three)"""
         with torch.cuda.graph(self.graph, stream=side, capture_error_mode="thread_local"):
-            if self._pull is not None:
+            if self._cycle is not None:
+                kn.micro_begin(self._cycle.words, self.counter)  # cycle position + seed offset += 1: one node
+            elif self._pull is not None:
                 self._pull.capture_node(self.counter)  # draws from the pinned ring + seed offset += 1: one node
             else:
                 self.counter.add_(1)
             self.total, self.losses = self._step_body()
+            if self._cycle is not None:
+                self._tail()
+
+    # ------------------------------------------------------------------ micro-batched replays (micro_steps=k)
+    def _check_micro_args(self, model, reducer, micro_steps, optimizer):
+        if micro_steps is None:
+            if optimizer is not None:
+                raise ValueError("%s: optimizer= captures the update of a micro-step cycle and needs micro_steps "
+                                 "(micro_steps=1 updates at every replay)" % type(self).__name__)
+            return
+        if not self.TRAIN:
+            raise ValueError("%s: micro_steps belongs to training steps" % type(self).__name__)
+        if int(micro_steps) < 1:
+            raise ValueError("micro_steps must be >= 1, got %r" % (micro_steps,))
+        if reducer is not None:
+            raise ValueError("%s: micro_steps together with reducer= is not supported: the collectives captured in the "
+                             "step graph cannot be gated by the cycle" % type(self).__name__)
+        if optimizer is not None:
+            from .optim import FlatAdamW
+            if not isinstance(optimizer, FlatAdamW):
+                raise ValueError("optimizer= takes a mesm_amd.optim.FlatAdamW (its update runs on the flat buffers), not %s"
+                                 % type(optimizer).__name__)
+            if optimizer.gb is not model.gradbuf() or optimizer.flat_p is None or optimizer.flat_p is not model.flat_params():
+                raise ValueError("optimizer= does not cover this model's flat buffers (it was built over another model, or "
+                                 "the parameters were flattened again after it was built)")
+
+    def _save_training_state(self):
+        gb = self.model.gradbuf()
+        torch.cuda.synchronize()
+        st = {"flat": gb.flat.clone(), "words": self._cycle.words.clone()}
+        opt = self.optimizer
+        if opt is not None:
+            st["opt"] = [(t, t.clone()) for t in (opt.flat_p, opt.exp_avg, opt.exp_avg_sq, opt.step_t)]
+            st["norm"] = opt._cap_norm.clone() if opt._cap_norm is not None else None
+        return st
+
+    def _restore_training_state(self, st):
+        gb = self.model.gradbuf()
+        cyc = self._cycle
+        torch.cuda.synchronize()
+        gb.flat.copy_(st["flat"])
+        cyc.words.copy_(st["words"])
+        for t, saved in st.get("opt", ()):
+            t.copy_(saved)
+        if st.get("norm") is not None:
+            self.optimizer._cap_norm.copy_(st["norm"])
+        # .grad of every tensor that some micro-stepped graph of the model writes aliases its view (the gradients of a
+        # cycle may come from several graphs): the same set after every capture, and what FlatAdamW.step() looks at
+        mine = [p.grad is not None for p in gb.params]
+        cyc.covered = [a or b for a, b in zip(cyc.covered, mine)] if cyc.covered is not None else mine
+        for p, on in zip(gb.params, cyc.covered):
+            p.grad = p._mesm_gview if on else None
+        torch.cuda.synchronize()
+
+    def _tail(self):
+        """behind the backward of a micro-stepped step: clip + AdamW update of the captured optimizer, gated by the
+        cycle's `due` word.  Outside a capture (warm-up) the coverage -- the tensors some graph of the model writes a
+        gradient for -- is brought up to date first (a host-to-device copy into the same mask tensor)."""
+        opt = self.optimizer
+        if opt is None:
+            return
+        gb, cyc = self.model.gradbuf(), self._cycle
+        mine = [p.grad is not None for p in gb.params]
+        union = [a or b for a, b in zip(cyc.covered, mine)] if cyc.covered is not None else mine
+        if torch.cuda.is_current_stream_capturing():
+            if union != cyc.covered:
+                raise RuntimeError("GraphedStep: the captured step writes gradients its warm-up step did not")
+        elif union != cyc.covered or opt._cap_tags is None:
+            cyc.covered = union
+            opt.set_coverage(union)
+        opt.step_gated(cyc.due_word, self.grad_clip)
+
+    def _extra_ptrs(self):
+        if self._cycle is None:
+            return []
+        extra = [self._cycle.words.data_ptr(), self._cycle.seed.data_ptr()]
+        if self.optimizer is not None:
+            extra += self.optimizer.captured_ptrs()
+        return extra
+
+    @property
+    def micro_steps(self):
+        return self._cycle.k if self._cycle is not None else None
+
+    @property
+    def update_due(self):
+        """after run(): that replay was the last of its cycle -- the buffer holds the mean gradient (and, with a captured
+        optimizer, the parameters have just been updated)"""
+        return self._cycle is not None and self._cycle.due
+
+    @property
+    def updates(self):
+        return self._cycle.updates if self._cycle is not None else 0
+
+    def set_micro_steps(self, k):
+        """another k from the next cycle on, without a new capture (k is a device word, the backward seed a tensor);
+        RuntimeError in the middle of a cycle"""
+        if self._cycle is None:
+            raise RuntimeError("%s was captured without micro_steps" % type(self).__name__)
+        self._cycle.set_k(k)
+
+    def reset_cycle(self):
+        """drop an unfinished cycle (the ragged end of an epoch): the next replay clears the gradient buffer"""
+        if self._cycle is None:
+            raise RuntimeError("%s was captured without micro_steps" % type(self).__name__)
+        self._cycle.reset()
 
     # ------------------------------------------------------------------ host half (shared with the loader workers)
     def _resolve_caps(self, caps, batch, group_cap=None):
@@ -263,7 +392,7 @@ class GraphedStep:
 
     def _param_ptrs(self):
         gb = self.model.gradbuf()
-        return [p.data_ptr() for p in gb.params] + [gb.flat.data_ptr()]
+        return [p.data_ptr() for p in gb.params] + [gb.flat.data_ptr()] + self._extra_ptrs()
 
     def _step_body(self):
         b = self.batch
@@ -273,6 +402,16 @@ class GraphedStep:
         # a hooked reducer launches its bucket collectives from inside and joins at the end; with fold_scale the
         # 1 / world of the gradient MEAN rides the loss gradient (one scalar) instead of a pass over the flat buffer
         sc = self.reducer.backward_scale() if self.reducer is not None else 1.0
+        if self._cycle is not None:
+            # 1 / k of the gradient MEAN rides the loss gradient, from the cycle's own tensor (set_micro_steps refills it);
+            # the clear of the flat buffer is gated by the cycle's phase and plain-autograd gradients are added to it
+            gb = self.model.gradbuf()
+            gb.gated = self._cycle
+            try:
+                total.backward(self._cycle.seed.view(total.shape))
+            finally:
+                gb.gated = None
+            return total.detach(), {k: v.detach() for k, v in losses.items()}
         # the seed of the backward pass from a tensor made once (autograd's own ones_like is a fill launch per step)
         seed = self._seed.get(sc)
         if seed is None or seed.shape != total.shape:
@@ -497,7 +636,7 @@ class GraphedStep:
         m = self.model
         gen = m.__dict__.get("_addr_gen", 0)
         fp = m._flat_params
-        quick = (fp.data_ptr() if fp is not None else 0, m.gradbuf().flat.data_ptr())
+        quick = (fp.data_ptr() if fp is not None else 0, m.gradbuf().flat.data_ptr()) + tuple(self._extra_ptrs())
         if gen != getattr(self, "_addr_gen", None) or quick != getattr(self, "_quick_ptrs", None):
             if self._param_ptrs() != self._ptrs:
                 raise RuntimeError("%s: a parameter or the gradient buffer moved after capture" % type(self).__name__)
@@ -511,6 +650,14 @@ class GraphedStep:
                 "Create the optimizer before the GraphedStep, or capture again.")
         if redraw:
             self.redraw()
+        if self._cycle is not None:
+            if self.optimizer is not None:
+                self.optimizer.check_captured()
+                self.optimizer.sync_hyperparameters()  # (a few float compares; a scheduler's new lr: one small copy)
+            self.graph.replay()
+            if self._cycle.advance(self.optimizer is not None) and self.optimizer is not None:
+                self.optimizer._opt_called = True  # (torch's schedulers warn unless they have seen an optimizer step)
+            return self.total
         self.graph.replay()
         return self.total
 
@@ -526,6 +673,9 @@ class SplitGraphedStep(GraphedStep):
     def __init__(self, *a, **kw):
         if kw.get("reducer") is not None:
             raise ValueError("SplitGraphedStep: gradient collectives ride in the one-graph step (GraphedStep)")
+        if kw.get("micro_steps") is not None or kw.get("optimizer") is not None:
+            raise ValueError("SplitGraphedStep: micro_steps / optimizer= belong to the one-graph step (GraphedStep): the "
+                             "caller of the three-graph step owns zero_grad and the optimizer")
         super().__init__(*a, **kw)
 
     def _capture(self, side):
@@ -743,7 +893,7 @@ class StepCache(GraphCache):
     dataset/base.py:164-207 -- and only a handful of distinct N.  `captures` counts the graphs built."""
 
     def __init__(self, model, criterion, dataset_name, reducer=None, max_graphs=16, pad=None, pairs=None,
-                 group_caps=None):
+                 group_caps=None, micro_steps=None, optimizer=None, grad_clip=0.0):
         """pairs: also pad the PAIR axis up to the next multiple of `pairs` (batching.pad_pairs: dummy pairs behind
         the real ones, the real count a device scalar of the captured step) -- the reference's loaders emit a different
         number of pairs almost every batch (an item is a video with all its queries, dataset/base.py:116-162), and
@@ -751,25 +901,49 @@ class StepCache(GraphCache):
         group_caps: ascending group-size buckets, e.g. (5, 9): a batch is served by a graph captured with room for
         video groups of up to the smallest bucket that holds its largest group (9 = the QVHighlights maximum), so that
         (pair bucket, group bucket) alone decide which graph a batch replays -- groups cost SS-MESM key slots
-        (group size x clips per pair), which is why there is more than one bucket."""
+        (group size x clips per pair), which is why there is more than one bucket.
+        micro_steps / optimizer / grad_clip: GraphedStep's, for every graph of the cache; the graphs share the model's
+        cycle state, so the micro-batches of one cycle may fall into different buckets."""
         super().__init__(max_graphs)
         self.model, self.crit, self.dataset_name = model, criterion, dataset_name
         self.reducer = reducer
+        self._micro = dict(micro_steps=micro_steps, optimizer=optimizer, grad_clip=grad_clip)
+        self._cycle = None
+        if micro_steps is not None or optimizer is not None:
+            GraphedStep._check_micro_args(self, model, reducer, micro_steps, optimizer)
+            self._cycle = model.gradbuf().cycle_state(next(model.parameters()).device)
+            self._cycle.set_k(micro_steps)
         self.pad = pad
         self.pairs = pairs
         self.group_caps = tuple(sorted(group_caps)) if group_caps else None
 
-    def run(self, batch, redraw=True):
+    def run(self, batch, redraw=True, draws=None):
+        """draws: (neg_index, masked_words) to replay with (GraphedStep.set_draws: tests, reproducing a recorded step)
+        instead of drawing"""
+        if draws is not None:
+            redraw = False
         batch = shape_batch(batch, self.pad, self.pairs)
         k = bucket_key(batch, self.group_caps)
         gs = self.find(k, lambda s: s.load_batch(batch, redraw=redraw))
         if gs is not None:
             self.replays += 1
+            if draws is not None:
+                gs.set_draws(*draws)
             return gs.run(redraw=False), gs
         dev = next(self.model.parameters()).device
         gs = self.add(k, lambda: GraphedStep(self.model, self.crit, capture_batch(batch, dev), self.dataset_name, warmup=1,
-                                             reducer=self.reducer, caps="auto", group_cap=k[2] if self.group_caps else None))
+                                             reducer=self.reducer, caps="auto", group_cap=k[2] if self.group_caps else None,
+                                             **self._micro))
+        if draws is not None:
+            gs.set_draws(*draws)
         return gs.run(redraw=redraw), gs
+
+    TRAIN = True
+    micro_steps = GraphedStep.micro_steps
+    update_due = GraphedStep.update_due
+    updates = GraphedStep.updates
+    set_micro_steps = GraphedStep.set_micro_steps
+    reset_cycle = GraphedStep.reset_cycle
 
     def pipeline(self, keep_raw=True):
         """the host half of `run` as a picklable object for loader workers (loader.HostPipeline).  keep_raw=False once

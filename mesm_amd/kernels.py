@@ -184,6 +184,21 @@ def fill_zero(t):
     check(lib().mesm_fill_ranges(ptrs, nb, 1, stream_ptr()), "mesm_fill_ranges")
 
 
+def fill_zero_gated(t, phase):
+    """fill_zero(t) iff the device word `phase` (int32) is 0 when the launch runs; otherwise nothing is written"""
+    assert phase.is_cuda and phase.dtype == torch.int32
+    ptrs = (ctypes.c_void_p * 1)(t.data_ptr())
+    nb = (ctypes.c_int64 * 1)(t.numel() * t.element_size())
+    check(lib().mesm_fill_ranges_gated(ptrs, nb, 1, ptr(phase), stream_ptr()), "mesm_fill_ranges_gated")
+
+
+def micro_begin(state, seed_ctr=None):
+    """first node of a micro-stepped graph (one thread): the four cycle words {count, k, phase, due} move on to this
+    replay and the dropout seed offset advances (csrc/glue.hip: micro_begin_kernel)"""
+    assert state.is_cuda and state.dtype == torch.int32 and state.numel() == 4 and state.is_contiguous()
+    check(lib().mesm_micro_begin(ptr(state), ptr(seed_ctr), stream_ptr()), "mesm_micro_begin")
+
+
 def zeros(shape, device):
     """fp32 zeros that live until the next step begins (see ZeroPool)"""
     return zero_pool.zeros(tuple(shape), device)

@@ -122,6 +122,7 @@ class FlatAdamW(torch.optim.Optimizer):
         self._table_slot = 0
         self._hyper_host = None
         self.last_norm = None
+        self._cap_tags = self._cap_partials = self._cap_norm = self._cap_baked = None
         if params is None:
             groups = [{"params": list(gb.params)}]
         else:
@@ -304,6 +305,75 @@ class FlatAdamW(torch.optim.Optimizer):
                                     float(grad_clip or 0.0), ptr(self.lr_t), float(b1), float(b2),
                                     float(g["eps"]), float(g["weight_decay"]), ptr(self.step_t),
                                     ptr(self.last_norm), stream_ptr()), "mesm_adamw_step")
+
+    # ------------------------------------------------------------------ the tail captured in a micro-stepped graph
+    def set_coverage(self, has_grad):
+        """Which tensors a CAPTURED update covers (graphed.GraphedStep(optimizer=...)): has_grad[i] for parameter i of
+        the gradient buffer -- some graph of the model writes its gradient -- instead of `p.grad is not None` at the time
+        of the call, which a replay cannot look at.  The mask / tag table of the captured launches is ONE device tensor,
+        rewritten in place (never from inside a capture), as are the partial sums and the norm (`last_norm`)."""
+        self._ensure()
+        gb = self.gb
+        host = tag_table(gb, self._group_of if self._grouped else [0] * len(gb.params), tuple(has_grad))
+        dev = self.flat_p.device
+        if self._cap_tags is None:
+            self._cap_tags = host.to(dev)
+            self._cap_partials = torch.zeros(1024, device=dev, dtype=torch.float32)
+            self._cap_norm = torch.zeros(1, device=dev, dtype=torch.float32)
+        else:
+            self._cap_tags.copy_(host)
+
+    def captured_ptrs(self):
+        """addresses a captured tail bakes in (GraphedStep compares them before every replay)"""
+        ts = (self.flat_p, self.exp_avg, self.exp_avg_sq, self.step_t, self.lr_t, self._table, self._cap_tags,
+              self._cap_partials, self._cap_norm)
+        return [t.data_ptr() if t is not None else 0 for t in ts]
+
+    @torch.no_grad()
+    def step_gated(self, due, grad_clip=0.0):
+        """`step(grad_clip=...)` as launches that act only when the device word `due` (int32, CycleState.due_word) is set:
+        otherwise nothing is written -- parameters, moments, step count and norm stay as they are.  Two launches, fixed
+        tensors only, so the pair can sit in a graph that is replayed at every micro-step.  The sum of squares runs
+        without clipping too: it is what advances the step count under the gate.  Coverage comes from set_coverage().
+        The default form reads lr from the device; betas, eps and weight_decay are launch arguments, fixed at capture
+        (`check_captured()` refuses a replay after they were edited); the grouped form reads all of them from its device
+        table."""
+        if self._cap_tags is None:
+            raise RuntimeError("FlatAdamW.step_gated: call set_coverage() first")
+        if not torch.cuda.is_current_stream_capturing():
+            self.sync_hyperparameters()
+        n_p = ctypes.c_int32(0)
+        flat = self.gb.flat
+        check(lib().mesm_grad_sumsq_gated(ptr(flat), flat.numel(), ptr(self._cap_partials), ctypes.byref(n_p),
+                                          ptr(self.step_t), ptr(due), stream_ptr()), "mesm_grad_sumsq_gated")
+        clip = float(grad_clip or 0.0)
+        clip = clip if clip > 0 else 0.0
+        self.last_norm = self._cap_norm
+        if self._grouped:
+            check(lib().mesm_adamw_step_groups_gated(ptr(self.flat_p), ptr(flat), ptr(self.exp_avg), ptr(self.exp_avg_sq),
+                                                     ptr(self._cap_tags), self.flat_p.numel(), ptr(self._cap_partials),
+                                                     n_p.value, clip, ptr(self._table), len(self._step0),
+                                                     ptr(self.step_t), ptr(self._cap_norm), ptr(due), stream_ptr()),
+                  "mesm_adamw_step_groups_gated")
+            return
+        g = self.param_groups[0]
+        b1, b2 = g["betas"]
+        self._cap_baked = (float(b1), float(b2), float(g["eps"]), float(g["weight_decay"]))
+        check(lib().mesm_adamw_step_gated(ptr(self.flat_p), ptr(flat), ptr(self.exp_avg), ptr(self.exp_avg_sq),
+                                          ptr(self._cap_tags), self.flat_p.numel(), ptr(self._cap_partials), n_p.value,
+                                          clip, ptr(self.lr_t), *self._cap_baked, ptr(self.step_t), ptr(self._cap_norm),
+                                          ptr(due), stream_ptr()), "mesm_adamw_step_gated")
+
+    def check_captured(self):
+        """before a replay of a captured step_gated(): RuntimeError when the default form's by-value hyperparameters
+        were edited since the capture (the replay would go on using the old ones)"""
+        if self._cap_baked is not None:
+            g = self.param_groups[0]
+            now = (float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]))
+            if now != self._cap_baked:
+                raise RuntimeError("FlatAdamW: betas / eps / weight_decay of the default form are fixed in a captured update "
+                                   "(%r at capture, %r now): capture again, or use parameter groups, whose hyperparameters "
+                                   "all live in device memory" % (self._cap_baked, now))
 
     def zero_grad(self, set_to_none=True):
         self.model.zero_grad(set_to_none=set_to_none)
