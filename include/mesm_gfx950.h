@@ -973,6 +973,44 @@ int mesm_adamw_step_groups_gated(float* p, const float* g, float* m, float* v, c
                                  const float* partials, int32_t np, float max_norm, const MesmAdamGroup* groups,
                                  int32_t n_groups, const int32_t* step, float* norm_out, const int32_t* due,
                                  void* stream);
+/* The four updates above with an exponential moving average (EMA) of the parameters kept in the same launch (no
+ * counterpart in the reference).  `ema` has the flat layout of p; for every group of 4 elements whose p the launch
+ * writes, and for no other (active / tag byte 0, a group that is not live yet, a gated launch that is not due), per
+ * element
+ *     e = fmaf(d, e - p_new, p_new)            (= d e + (1 - d) p_new; e == p_new is an exact fixed point)
+ * with p_new the value just stored.  d is uniform: with n = *step - 1 - es->step0 (the averages taken before this one;
+ * *step as this update sees it, after the increment of mesm_grad_sumsq or the host; a negative n counts as 0),
+ *     d = es->warmup ? min(es->decay, (1 + n) / (10 + n)) : es->decay          (IEEE float arithmetic)
+ * and is also written to *decay_out (optional, like norm_out).  p, m, v, *step and *norm_out are the twin entry's bit for
+ * bit.  Each entry has its twin's checks, plus MESM_EINVAL for a null ema or es (es: 4-byte aligned) and MESM_EALIGN for
+ * an ema off a 16-byte boundary.
+ *   mesm_swap_f32   exchanges the contents of two flat buffers in place (n % 4 == 0, both 16-byte aligned, not
+ *                   overlapping unless a == b): evaluating with the averaged weights moves no address. */
+typedef struct MesmEmaState { /* 16 bytes, lives in DEVICE memory */
+  float decay;     /* 0 < decay < 1 */
+  int32_t warmup;  /* != 0: the decay rises as (1 + n) / (10 + n) up to `decay` */
+  int32_t step0;   /* *step when the average was last set equal to the parameters */
+  int32_t reserved;
+} MesmEmaState;
+int mesm_adamw_step_ema(float* p, const float* g, float* m, float* v, const uint8_t* active4, int64_t n,
+                        const float* partials, int32_t np, float max_norm, const float* lr, float beta1,
+                        float beta2, float eps, float weight_decay, const int32_t* step, float* norm_out,
+                        float* ema, const MesmEmaState* es, float* decay_out, void* stream);
+int mesm_adamw_step_ema_gated(float* p, const float* g, float* m, float* v, const uint8_t* active4, int64_t n,
+                              const float* partials, int32_t np, float max_norm, const float* lr, float beta1,
+                              float beta2, float eps, float weight_decay, const int32_t* step, float* norm_out,
+                              const int32_t* due, float* ema, const MesmEmaState* es, float* decay_out,
+                              void* stream);
+int mesm_adamw_step_groups_ema(float* p, const float* g, float* m, float* v, const uint8_t* tag4, int64_t n,
+                               const float* partials, int32_t np, float max_norm, const MesmAdamGroup* groups,
+                               int32_t n_groups, const int32_t* step, float* norm_out, float* ema,
+                               const MesmEmaState* es, float* decay_out, void* stream);
+int mesm_adamw_step_groups_ema_gated(float* p, const float* g, float* m, float* v, const uint8_t* tag4, int64_t n,
+                                     const float* partials, int32_t np, float max_norm,
+                                     const MesmAdamGroup* groups, int32_t n_groups, const int32_t* step,
+                                     float* norm_out, const int32_t* due, float* ema, const MesmEmaState* es,
+                                     float* decay_out, void* stream);
+int mesm_swap_f32(float* a, float* b, int64_t n, void* stream);
 
 /* ------------------------------------------------------------------------- */
 /*

@@ -137,6 +137,13 @@ class AdamGroup(ctypes.Structure):
 
 ADAM_MAX_GROUPS = 64
 
+
+class EmaState(ctypes.Structure):
+    """MesmEmaState: decay, warm-up switch and starting step of FlatAdamW's weight EMA, in device memory"""
+    _fields_ = [("decay", ctypes.c_float), ("warmup", ctypes.c_int32), ("step0", ctypes.c_int32),
+                ("reserved", ctypes.c_int32)]
+
+
 # name -> (restype, argtypes); mirrors include/mesm_gfx950.h one to one.
 _i32, _i64, _f32, _u32 = ctypes.c_int32, ctypes.c_int64, ctypes.c_float, ctypes.c_uint32
 PROTOTYPES = {
@@ -257,6 +264,15 @@ PROTOTYPES = {
                                              c_ptr, c_ptr, c_ptr, c_ptr]),
     "mesm_adamw_step_groups_gated": (ctypes.c_int, [c_ptr] * 5 + [_i64, c_ptr, _i32, _f32, c_ptr, _i32, c_ptr, c_ptr,
                                                     c_ptr, c_ptr]),
+    "mesm_adamw_step_ema": (ctypes.c_int, [c_ptr] * 5 + [_i64, c_ptr, _i32, _f32, c_ptr, _f32, _f32, _f32, _f32,
+                                           c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
+    "mesm_adamw_step_ema_gated": (ctypes.c_int, [c_ptr] * 5 + [_i64, c_ptr, _i32, _f32, c_ptr, _f32, _f32, _f32, _f32,
+                                                 c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
+    "mesm_adamw_step_groups_ema": (ctypes.c_int, [c_ptr] * 5 + [_i64, c_ptr, _i32, _f32, c_ptr, _i32, c_ptr, c_ptr,
+                                                  c_ptr, c_ptr, c_ptr, c_ptr]),
+    "mesm_adamw_step_groups_ema_gated": (ctypes.c_int, [c_ptr] * 5 + [_i64, c_ptr, _i32, _f32, c_ptr, _i32, c_ptr, c_ptr,
+                                                        c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
+    "mesm_swap_f32": (ctypes.c_int, [c_ptr, c_ptr, _i64, c_ptr]),
     "mesm_glue_group": (ctypes.c_int, [ctypes.POINTER(GlueArgs), _i32, c_ptr]),
     "mesm_criterion_fwd": (ctypes.c_int, [ctypes.POINTER(CritFwdArgs), c_ptr]),
     "mesm_criterion_bwd": (ctypes.c_int, [ctypes.POINTER(CritBwdArgs), c_ptr]),

@@ -66,14 +66,35 @@ __global__ __launch_bounds__(OPT_THREADS) void clip_scale_kernel(float* __restri
   }
 }
 
+// decay of the EMA update that goes with step count `t` (the count AFTER this update's increment): n = t - 1 - step0
+// averages have been taken before it; with warm-up the decay rises as (1 + n) / (10 + n) up to es->decay.  Uniform, plain
+// IEEE float arithmetic; optim.py's ema_decay_at is the host mirror.
+__device__ __forceinline__ float ema_decay(const MesmEmaState* __restrict__ es, int32_t t) {
+  const int32_t n = t - 1 - es->step0;
+  const float d = es->decay;
+  const float nf = (float)(n < 0 ? 0 : n);
+  return es->warmup ? fminf(d, (1.0f + nf) / (10.0f + nf)) : d;
+}
+
+// e = d * e + (1 - d) * p as one subtract and one FMA: e == p is an exact fixed point
+__device__ __forceinline__ float4 ema_update(float d, const float4 e, const float (&pe)[4]) {
+  return make_float4(fmaf(d, e.x - pe[0], pe[0]), fmaf(d, e.y - pe[1], pe[1]), fmaf(d, e.z - pe[2], pe[2]),
+                     fmaf(d, e.w - pe[3], pe[3]));
+}
+
 // AdamW on groups of 4 elements; active4[i] == 0 skips group i (parameters that have no gradient this
 // step are left untouched, exactly like torch.optim skips p.grad is None: no decay, no state update)
-template <bool GATED>
+//
+// EMA instantiations (the *_ema entries) also keep an exponential moving average of the parameters in `ema`, a buffer with
+// p's layout: every group of 4 whose p is written, and no other, gets e = d * e + (1 - d) * p_new from the registers that
+// hold p_new.  The other instantiations never look at the three arguments.
+template <bool GATED, bool EMA>
 __global__ __launch_bounds__(OPT_THREADS) void adamw_kernel(
     float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
     const uint8_t* __restrict__ active4, int64_t n4, const float* __restrict__ partials, int np,
     float max_norm, const float* __restrict__ lr_p, float beta1, float beta2, float eps, float wd,
-    const int32_t* __restrict__ step, float* __restrict__ norm_out, const int32_t* __restrict__ due) {
+    const int32_t* __restrict__ step, float* __restrict__ norm_out, const int32_t* __restrict__ due,
+    float* __restrict__ ema, const MesmEmaState* __restrict__ es, float* __restrict__ decay_out) {
   if constexpr (GATED) {
     if (due[0] == 0) return;
   }
@@ -91,12 +112,19 @@ __global__ __launch_bounds__(OPT_THREADS) void adamw_kernel(
   const float step_size = lr / bc1;
   const float inv_sqrt_bc2 = 1.0f / sqrtf(bc2);
   const float decay = 1.0f - lr * wd;
+  float ed = 0.0f;
+  if constexpr (EMA) {
+    ed = ema_decay(es, step[0]);
+    if (blockIdx.x == 0 && threadIdx.x == 0 && decay_out) decay_out[0] = ed;
+  }
   for (int64_t i = (int64_t)blockIdx.x * OPT_THREADS + threadIdx.x; i < n4; i += (int64_t)gridDim.x * OPT_THREADS) {
     if (active4 && !active4[i]) continue;
     float4 pv = reinterpret_cast<float4*>(p)[i];
     const float4 gv = reinterpret_cast<const float4*>(g)[i];
     float4 mv = reinterpret_cast<float4*>(m)[i];
     float4 vv = reinterpret_cast<float4*>(v)[i];
+    float4 ev;
+    if constexpr (EMA) ev = reinterpret_cast<float4*>(ema)[i];
     float pe[4] = {pv.x, pv.y, pv.z, pv.w}, ge[4] = {gv.x, gv.y, gv.z, gv.w};
     float me[4] = {mv.x, mv.y, mv.z, mv.w}, ve[4] = {vv.x, vv.y, vv.z, vv.w};
 #pragma unroll
@@ -111,6 +139,7 @@ __global__ __launch_bounds__(OPT_THREADS) void adamw_kernel(
     reinterpret_cast<float4*>(p)[i] = make_float4(pe[0], pe[1], pe[2], pe[3]);
     reinterpret_cast<float4*>(m)[i] = make_float4(me[0], me[1], me[2], me[3]);
     reinterpret_cast<float4*>(v)[i] = make_float4(ve[0], ve[1], ve[2], ve[3]);
+    if constexpr (EMA) reinterpret_cast<float4*>(ema)[i] = ema_update(ed, ev, pe);
   }
 }
 
@@ -124,12 +153,14 @@ struct alignas(16) GroupConsts {
 // once per workgroup from the device table, with adamw_kernel's float expressions (one group over the whole buffer gives
 // adamw_kernel's bits), and kept in LDS; the per-element work is adamw_kernel's plus that indexed read, which is
 // wave-uniform except where two tensors of different groups meet inside a wave.
-template <bool GATED>
+// EMA: as in adamw_kernel; a group that is not live leaves its average alone like its p, m and v.
+template <bool GATED, bool EMA>
 __global__ __launch_bounds__(OPT_THREADS) void adamw_groups_kernel(
     float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
     const uint8_t* __restrict__ tag4, int64_t n4, const float* __restrict__ partials, int np, float max_norm,
     const MesmAdamGroup* __restrict__ groups, int n_groups, const int32_t* __restrict__ step,
-    float* __restrict__ norm_out, const int32_t* __restrict__ due) {
+    float* __restrict__ norm_out, const int32_t* __restrict__ due, float* __restrict__ ema,
+    const MesmEmaState* __restrict__ es, float* __restrict__ decay_out) {
   if constexpr (GATED) {
     if (due[0] == 0) return;
   }
@@ -161,6 +192,11 @@ __global__ __launch_bounds__(OPT_THREADS) void adamw_groups_kernel(
     gc[threadIdx.x] = c;
     live[threadIdx.x] = ti >= 1;
   }
+  float ed = 0.0f;
+  if constexpr (EMA) {
+    ed = ema_decay(es, step[0]);
+    if (blockIdx.x == 0 && threadIdx.x == 0 && decay_out) decay_out[0] = ed;
+  }
   __syncthreads();
   for (int64_t i = (int64_t)blockIdx.x * OPT_THREADS + threadIdx.x; i < n4; i += (int64_t)gridDim.x * OPT_THREADS) {
     const uint32_t k = (uint32_t)tag4[i] - 1u;  // tag 0 wraps past every group
@@ -171,6 +207,8 @@ __global__ __launch_bounds__(OPT_THREADS) void adamw_groups_kernel(
     const float4 gv = reinterpret_cast<const float4*>(g)[i];
     float4 mv = reinterpret_cast<float4*>(m)[i];
     float4 vv = reinterpret_cast<float4*>(v)[i];
+    float4 ev;
+    if constexpr (EMA) ev = reinterpret_cast<float4*>(ema)[i];
     float pe[4] = {pv.x, pv.y, pv.z, pv.w}, ge[4] = {gv.x, gv.y, gv.z, gv.w};
     float me[4] = {mv.x, mv.y, mv.z, mv.w}, ve[4] = {vv.x, vv.y, vv.z, vv.w};
 #pragma unroll
@@ -186,6 +224,18 @@ __global__ __launch_bounds__(OPT_THREADS) void adamw_groups_kernel(
     reinterpret_cast<float4*>(p)[i] = make_float4(pe[0], pe[1], pe[2], pe[3]);
     reinterpret_cast<float4*>(m)[i] = make_float4(me[0], me[1], me[2], me[3]);
     reinterpret_cast<float4*>(v)[i] = make_float4(ve[0], ve[1], ve[2], ve[3]);
+    if constexpr (EMA) reinterpret_cast<float4*>(ema)[i] = ema_update(ed, ev, pe);
+  }
+}
+
+// a <-> b in place, 16 bytes per lane and pass: every float4 is read from both buffers and written to both by the one
+// lane that owns it, so there is no temporary and no ordering between lanes to respect
+__global__ __launch_bounds__(OPT_THREADS) void swap_kernel(float* __restrict__ a, float* __restrict__ b, int64_t n4) {
+  for (int64_t i = (int64_t)blockIdx.x * OPT_THREADS + threadIdx.x; i < n4; i += (int64_t)gridDim.x * OPT_THREADS) {
+    const float4 x = reinterpret_cast<float4*>(a)[i];
+    const float4 y = reinterpret_cast<float4*>(b)[i];
+    reinterpret_cast<float4*>(a)[i] = y;
+    reinterpret_cast<float4*>(b)[i] = x;
   }
 }
 
@@ -208,31 +258,48 @@ int grad_sumsq(const float* g, int64_t n, float* partials, int32_t* np_out, int3
   return mesm_launch_status();
 }
 
-template <bool GATED>
+// the checks the *_ema entries add to their twins' (after the twin's own MESM_EINVAL checks, before its alignment ones)
+inline int ema_check(const float* ema, const MesmEmaState* es) {
+  if (!ema || !es || ((uintptr_t)es & 3)) return MESM_EINVAL;
+  if ((uintptr_t)ema & 15) return MESM_EALIGN;
+  return 0;
+}
+
+template <bool GATED, bool EMA>
 int adamw_step(float* p, const float* g, float* m, float* v, const uint8_t* active4, int64_t n, const float* partials,
                int32_t np, float max_norm, const float* lr, float beta1, float beta2, float eps, float weight_decay,
-               const int32_t* step, float* norm_out, const int32_t* due, void* stream) {
+               const int32_t* step, float* norm_out, const int32_t* due, float* ema, const MesmEmaState* es,
+               float* decay_out, void* stream) {
   if (!p || !g || !m || !v || !lr || !step || n <= 0 || (n & 3)) return MESM_EINVAL;
   if (GATED && (!due || ((uintptr_t)due & 3))) return MESM_EINVAL;
   if (max_norm > 0.f && (!partials || np <= 0 || np > 1024)) return MESM_EINVAL;
+  if (EMA) {
+    if (const int rc = ema_check(ema, es)) return rc;
+  }
   if ((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) != 0) return MESM_EALIGN;
-  hipLaunchKernelGGL(adamw_kernel<GATED>, dim3(opt_blocks(n / 4)), dim3(OPT_THREADS), 0, (hipStream_t)stream, p, g, m,
-                     v, active4, n / 4, partials, np, max_norm, lr, beta1, beta2, eps, weight_decay, step, norm_out, due);
+  hipLaunchKernelGGL((adamw_kernel<GATED, EMA>), dim3(opt_blocks(n / 4)), dim3(OPT_THREADS), 0, (hipStream_t)stream, p,
+                     g, m, v, active4, n / 4, partials, np, max_norm, lr, beta1, beta2, eps, weight_decay, step, norm_out,
+                     due, ema, es, decay_out);
   return mesm_launch_status();
 }
 
-template <bool GATED>
+template <bool GATED, bool EMA>
 int adamw_step_groups(float* p, const float* g, float* m, float* v, const uint8_t* tag4, int64_t n,
                       const float* partials, int32_t np, float max_norm, const MesmAdamGroup* groups, int32_t n_groups,
-                      const int32_t* step, float* norm_out, const int32_t* due, void* stream) {
+                      const int32_t* step, float* norm_out, const int32_t* due, float* ema, const MesmEmaState* es,
+                      float* decay_out, void* stream) {
   if (!p || !g || !m || !v || !tag4 || !groups || !step || n <= 0 || (n & 3)) return MESM_EINVAL;
   if (GATED && (!due || ((uintptr_t)due & 3))) return MESM_EINVAL;
   if (n_groups < 1 || n_groups > MESM_ADAM_MAX_GROUPS) return MESM_EINVAL;
   if (max_norm > 0.f && (!partials || np <= 0 || np > 1024)) return MESM_EINVAL;
+  if (EMA) {
+    if (const int rc = ema_check(ema, es)) return rc;
+  }
   if ((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) != 0) return MESM_EALIGN;
   if (((uintptr_t)groups & 3) != 0) return MESM_EALIGN;
-  hipLaunchKernelGGL(adamw_groups_kernel<GATED>, dim3(opt_blocks(n / 4)), dim3(OPT_THREADS), 0, (hipStream_t)stream, p,
-                     g, m, v, tag4, n / 4, partials, np, max_norm, groups, n_groups, step, norm_out, due);
+  hipLaunchKernelGGL((adamw_groups_kernel<GATED, EMA>), dim3(opt_blocks(n / 4)), dim3(OPT_THREADS), 0,
+                     (hipStream_t)stream, p, g, m, v, tag4, n / 4, partials, np, max_norm, groups, n_groups, step, norm_out,
+                     due, ema, es, decay_out);
   return mesm_launch_status();
 }
 
@@ -260,30 +327,74 @@ extern "C" int mesm_adamw_step(float* p, const float* g, float* m, float* v, con
                                const float* partials, int32_t np, float max_norm, const float* lr,
                                float beta1, float beta2, float eps, float weight_decay, const int32_t* step,
                                float* norm_out, void* stream) {
-  return adamw_step<false>(p, g, m, v, active4, n, partials, np, max_norm, lr, beta1, beta2, eps, weight_decay, step,
-                           norm_out, nullptr, stream);
+  return adamw_step<false, false>(p, g, m, v, active4, n, partials, np, max_norm, lr, beta1, beta2, eps, weight_decay,
+                                  step, norm_out, nullptr, nullptr, nullptr, nullptr, stream);
 }
 
 extern "C" int mesm_adamw_step_gated(float* p, const float* g, float* m, float* v, const uint8_t* active4, int64_t n,
                                      const float* partials, int32_t np, float max_norm, const float* lr,
                                      float beta1, float beta2, float eps, float weight_decay, const int32_t* step,
                                      float* norm_out, const int32_t* due, void* stream) {
-  return adamw_step<true>(p, g, m, v, active4, n, partials, np, max_norm, lr, beta1, beta2, eps, weight_decay, step,
-                          norm_out, due, stream);
+  return adamw_step<true, false>(p, g, m, v, active4, n, partials, np, max_norm, lr, beta1, beta2, eps, weight_decay,
+                                 step, norm_out, due, nullptr, nullptr, nullptr, stream);
 }
 
 extern "C" int mesm_adamw_step_groups(float* p, const float* g, float* m, float* v, const uint8_t* tag4, int64_t n,
                                       const float* partials, int32_t np, float max_norm,
                                       const MesmAdamGroup* groups, int32_t n_groups, const int32_t* step,
                                       float* norm_out, void* stream) {
-  return adamw_step_groups<false>(p, g, m, v, tag4, n, partials, np, max_norm, groups, n_groups, step, norm_out,
-                                  nullptr, stream);
+  return adamw_step_groups<false, false>(p, g, m, v, tag4, n, partials, np, max_norm, groups, n_groups, step, norm_out,
+                                         nullptr, nullptr, nullptr, nullptr, stream);
 }
 
 extern "C" int mesm_adamw_step_groups_gated(float* p, const float* g, float* m, float* v, const uint8_t* tag4,
                                             int64_t n, const float* partials, int32_t np, float max_norm,
                                             const MesmAdamGroup* groups, int32_t n_groups, const int32_t* step,
                                             float* norm_out, const int32_t* due, void* stream) {
-  return adamw_step_groups<true>(p, g, m, v, tag4, n, partials, np, max_norm, groups, n_groups, step, norm_out, due,
-                                 stream);
+  return adamw_step_groups<true, false>(p, g, m, v, tag4, n, partials, np, max_norm, groups, n_groups, step, norm_out,
+                                        due, nullptr, nullptr, nullptr, stream);
+}
+
+// ---- the four updates with the weight EMA fused in (their twins' argument lists with ema, es, decay_out before stream)
+extern "C" int mesm_adamw_step_ema(float* p, const float* g, float* m, float* v, const uint8_t* active4, int64_t n,
+                                   const float* partials, int32_t np, float max_norm, const float* lr, float beta1,
+                                   float beta2, float eps, float weight_decay, const int32_t* step, float* norm_out,
+                                   float* ema, const MesmEmaState* es, float* decay_out, void* stream) {
+  return adamw_step<false, true>(p, g, m, v, active4, n, partials, np, max_norm, lr, beta1, beta2, eps, weight_decay,
+                                 step, norm_out, nullptr, ema, es, decay_out, stream);
+}
+
+extern "C" int mesm_adamw_step_ema_gated(float* p, const float* g, float* m, float* v, const uint8_t* active4,
+                                         int64_t n, const float* partials, int32_t np, float max_norm, const float* lr,
+                                         float beta1, float beta2, float eps, float weight_decay, const int32_t* step,
+                                         float* norm_out, const int32_t* due, float* ema, const MesmEmaState* es,
+                                         float* decay_out, void* stream) {
+  return adamw_step<true, true>(p, g, m, v, active4, n, partials, np, max_norm, lr, beta1, beta2, eps, weight_decay,
+                                step, norm_out, due, ema, es, decay_out, stream);
+}
+
+extern "C" int mesm_adamw_step_groups_ema(float* p, const float* g, float* m, float* v, const uint8_t* tag4, int64_t n,
+                                          const float* partials, int32_t np, float max_norm,
+                                          const MesmAdamGroup* groups, int32_t n_groups, const int32_t* step,
+                                          float* norm_out, float* ema, const MesmEmaState* es, float* decay_out,
+                                          void* stream) {
+  return adamw_step_groups<false, true>(p, g, m, v, tag4, n, partials, np, max_norm, groups, n_groups, step, norm_out,
+                                        nullptr, ema, es, decay_out, stream);
+}
+
+extern "C" int mesm_adamw_step_groups_ema_gated(float* p, const float* g, float* m, float* v, const uint8_t* tag4,
+                                                int64_t n, const float* partials, int32_t np, float max_norm,
+                                                const MesmAdamGroup* groups, int32_t n_groups, const int32_t* step,
+                                                float* norm_out, const int32_t* due, float* ema,
+                                                const MesmEmaState* es, float* decay_out, void* stream) {
+  return adamw_step_groups<true, true>(p, g, m, v, tag4, n, partials, np, max_norm, groups, n_groups, step, norm_out,
+                                       due, ema, es, decay_out, stream);
+}
+
+extern "C" int mesm_swap_f32(float* a, float* b, int64_t n, void* stream) {
+  if (!a || !b || n <= 0 || (n & 3)) return MESM_EINVAL;
+  if ((((uintptr_t)a | (uintptr_t)b) & 15) != 0) return MESM_EALIGN;
+  if (a == b) return 0;
+  hipLaunchKernelGGL(swap_kernel, dim3(opt_blocks(n / 4)), dim3(OPT_THREADS), 0, (hipStream_t)stream, a, b, n / 4);
+  return mesm_launch_status();
 }

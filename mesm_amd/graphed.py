@@ -305,7 +305,11 @@ class GraphedStep:
         st = {"flat": gb.flat.clone(), "words": self._cycle.words.clone()}
         opt = self.optimizer
         if opt is not None:
-            st["opt"] = [(t, t.clone()) for t in (opt.flat_p, opt.exp_avg, opt.exp_avg_sq, opt.step_t)]
+            # host edits of the hyperparameters reach the device BEFORE the snapshot: the warm-up passes would upload them
+            # after it, and the restore would put the old device words back under a host that believes them current
+            opt.sync_hyperparameters()
+            # (with a weight EMA: the average, its decay words and the decay of the last update as well)
+            st["opt"] = [(t, t.clone()) for t in [opt.flat_p, opt.exp_avg, opt.exp_avg_sq, opt.step_t] + opt.ema_tensors()]
             st["norm"] = opt._cap_norm.clone() if opt._cap_norm is not None else None
         return st
 

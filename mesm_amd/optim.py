@@ -30,9 +30,19 @@ Parameter groups (the `param_dicts` form of runner.py:349) and partial coverage:
 Still two launches: one tag byte per 4 elements of the flat layout names the group (0: not covered, or no
 gradient this step), and lr / betas / eps / weight_decay of every group live in a small device table, so
 a captured `step()` follows what schedulers and users write into `param_groups`.
+
+Weight EMA (`ema_decay=`): an exponential moving average of the parameters, kept by the SAME update launch in a third
+flat buffer -- train on the raw weights, evaluate and checkpoint the averaged ones:
+
+    optimizer = FlatAdamW(model, lr=opt.lr, ema_decay=0.999, ema_warmup=True)
+    ...
+    with optimizer.swap_ema():              # the parameters hold the average inside the block; no address moves
+        eval_epoch(model, ...)
 """
+import contextlib
 import ctypes
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -85,6 +95,24 @@ def _v_scale(beta2, t):
     return (1.0 - beta2 ** t) / (1.0 - b2f ** t)
 
 
+def ema_decay_at(n, decay, warmup):
+    """The decay of the EMA update that follows `n` earlier ones, as numpy.float32: the host mirror of the kernels'
+    expression (csrc/optim.hip: ema_decay), operation for operation.  Without warm-up it is `decay`; with it the average
+    starts close to the weights and settles: min(decay, (1 + n) / (10 + n))."""
+    d = np.float32(decay)
+    if not warmup:
+        return d
+    nf = np.float32(max(int(n), 0))
+    return np.minimum(d, (np.float32(1.0) + nf) / (np.float32(10.0) + nf))
+
+
+def _check_ema_decay(decay):
+    d = ctypes.c_float(float(decay)).value  # (what the kernel sees)
+    if not 0.0 < d < 1.0:
+        raise ValueError("ema_decay must satisfy 0 < ema_decay < 1 as a float32, got %r" % (decay,))
+    return float(decay)
+
+
 class FlatAdamW(torch.optim.Optimizer):
     """torch.optim.AdamW semantics (decoupled weight decay, bias correction, eps outside the sqrt of
     the bias-corrected second moment, amsgrad off) over flat buffers.
@@ -103,10 +131,26 @@ class FlatAdamW(torch.optim.Optimizer):
     rebuilt on the host.
 
     `state_dict()` / `load_state_dict()` speak torch.optim.AdamW's format with the same grouping, in both directions;
-    with groups, exp_avg_sq is written in torch's convention (`_v_scale`)."""
+    with groups, exp_avg_sq is written in torch's convention (`_v_scale`).
+
+    `ema_decay=d` (None: off, and nothing below exists) keeps e = d * e + (1 - d) * p in a flat buffer `ema` for every
+    element an update writes, inside the update's own launch (the *_ema entries); tensors an update skips keep their
+    average.  With `ema_warmup` the n-th update uses min(d, (1 + n) / (10 + n)) (`ema_decay_at`).  `ema_decay` and
+    `ema_warmup` are attributes: an edit reaches the device with the next `sync_hyperparameters()`, in the same device
+    words, so a captured update follows it without a new capture; `last_ema_decay` is the decay the last update used (a
+    device scalar).  The average starts as a copy of the weights and starts over (`reset_ema()`) whenever
+    `model.load_state_dict` brings other weights.  `swap_ema()` exchanges weights and average in place for evaluation,
+    `ema_state_dict()` gives the average under the model's key names, and `state_dict()` carries it under "ema"."""
 
     def __init__(self, model, params=None, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2,
-                 amsgrad=False, maximize=False):
+                 amsgrad=False, maximize=False, ema_decay=None, ema_warmup=False):
+        self._ema_on = ema_decay is not None
+        self._ema_decay = _check_ema_decay(ema_decay) if self._ema_on else None
+        self.ema_warmup = bool(ema_warmup)
+        self.ema = self._ema_state = self.last_ema_decay = None
+        self._ema_step0 = 0
+        self._ema_host = None
+        self._swapped = False
         self.model = model
         gb = model.gradbuf()
         self.gb = gb
@@ -136,6 +180,10 @@ class FlatAdamW(torch.optim.Optimizer):
             # constructor sees the final parameter addresses (model.flat_params is idempotent and
             # build_model has normally done it already)
             self._ensure()
+        if self._ema_on:
+            # other weights loaded into the model later must not leave a stale average behind (a resumed optimizer state
+            # is loaded after the model and puts its own average back: checkpoint.load_checkpoint)
+            model.register_load_state_dict_post_hook(lambda module, incompatible: self.reset_ema())
 
     # ------------------------------------------------------------------ groups
     def _name_of(self, p):
@@ -199,6 +247,12 @@ class FlatAdamW(torch.optim.Optimizer):
         self.exp_avg_sq = torch.zeros_like(self.flat_p)
         self.step_t = torch.zeros(1, device=dev, dtype=torch.int32)
         self.lr_t = torch.full((1,), float(self.param_groups[0]["lr"]), device=dev, dtype=torch.float32)
+        if self._ema_on:
+            self.ema = self.flat_p.clone()
+            self._ema_state = torch.zeros(ctypes.sizeof(_lib.EmaState), device=dev, dtype=torch.uint8)
+            self.last_ema_decay = torch.zeros(1, device=dev, dtype=torch.float32)
+            self._ema_step0, self._ema_host = 0, None
+            self._sync_ema()  # (the device words are valid from here on, whoever reads or snapshots them)
         if self._grouped:
             nbytes = _lib.ADAM_MAX_GROUPS * ctypes.sizeof(_lib.AdamGroup)
             self._table = torch.zeros(nbytes, device=dev, dtype=torch.uint8)
@@ -250,6 +304,8 @@ class FlatAdamW(torch.optim.Optimizer):
         the host).  Costs a comparison of a few floats per group when nothing changed; otherwise one small copy from
         a pinned buffer into the same device tensor, so a captured step() sees the new values at its next replay."""
         self._ensure()
+        if self._ema_on:
+            self._sync_ema()
         if not self._grouped:
             g = self.param_groups[0]
             if float(g["lr"]) != getattr(self, "_lr_host", None):  # StepLR edits param_groups[0]["lr"]
@@ -275,6 +331,107 @@ class FlatAdamW(torch.optim.Optimizer):
         self._table_events[slot].record()
         self._hyper_host = hyper
 
+    # ------------------------------------------------------------------ weight EMA
+    @property
+    def ema_decay(self):
+        return self._ema_decay
+
+    @ema_decay.setter
+    def ema_decay(self, value):
+        if not self._ema_on:
+            raise RuntimeError("FlatAdamW was built without ema_decay: there is no EMA buffer to average into")
+        self._ema_decay = _check_ema_decay(value)
+
+    def _sync_ema(self):
+        """decay, warm-up switch and starting step into the device's MesmEmaState when they changed on the host"""
+        cur = (self._ema_decay, bool(self.ema_warmup), self._ema_step0)
+        if cur == self._ema_host:
+            return
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("the EMA settings changed: call sync_hyperparameters() before capturing step()")
+        st = _lib.EmaState(decay=cur[0], warmup=int(cur[1]), step0=cur[2], reserved=0)
+        self._ema_state.copy_(torch.frombuffer(bytearray(bytes(st)), dtype=torch.uint8))
+        self._ema_host = cur
+
+    def _ema_args(self):
+        if self._swapped:
+            raise RuntimeError("FlatAdamW: no update inside swap_ema() (the parameters hold the average)")
+        return ptr(self.ema), ptr(self._ema_state), ptr(self.last_ema_decay)
+
+    def _need_ema(self, what):
+        if not self._ema_on:
+            raise RuntimeError("FlatAdamW.%s: the optimizer was built without ema_decay" % what)
+        self._ensure()
+
+    def ema_tensors(self):
+        """what the EMA adds to the optimizer's device state ([] when it is off): the average, the MesmEmaState words and
+        the decay of the last update"""
+        return [self.ema, self._ema_state, self.last_ema_decay] if self.ema is not None else []
+
+    @property
+    def num_updates(self):
+        """EMA updates since the average was last set equal to the weights (reads the device's step count)"""
+        self._need_ema("num_updates")
+        return int(self.step_t.item()) - self._ema_step0
+
+    @torch.no_grad()
+    def reset_ema(self):
+        """ema := the current weights, and the warm-up schedule starts over"""
+        if not self._ema_on:
+            raise RuntimeError("FlatAdamW.reset_ema: the optimizer was built without ema_decay")
+        if self.flat_p is None:  # (no flat state yet: the average will start as a copy of whatever the weights are then)
+            return
+        if self._swapped:
+            raise RuntimeError("FlatAdamW.reset_ema: not inside swap_ema()")
+        self.ema.copy_(self.flat_p)
+        self._ema_step0 = int(self.step_t.item())
+        self._sync_ema()
+
+    def _swap(self):
+        check(lib().mesm_swap_f32(ptr(self.flat_p), ptr(self.ema), self.flat_p.numel(), stream_ptr()), "mesm_swap_f32")
+
+    @contextlib.contextmanager
+    def swap_ema(self):
+        """Inside the block the parameters hold the averaged weights and `ema` holds the raw ones: the CONTENTS of the two
+        flat buffers are exchanged (one launch) and exchanged back on exit.  No address moves, so modules, views and
+        every captured training or evaluation graph stay valid.  step(), step_gated() and replays of a captured update
+        raise RuntimeError inside; so does nesting."""
+        self._need_ema("swap_ema")
+        if self._swapped:
+            raise RuntimeError("FlatAdamW.swap_ema: already inside swap_ema()")
+        self._swap()
+        self._swapped = True
+        try:
+            yield self
+        finally:
+            self._swap()
+            self._swapped = False
+
+    def _ema_src(self):
+        return self.flat_p if self._swapped else self.ema
+
+    def ema_state_dict(self):
+        """{name: averaged tensor} for every tensor of the gradient buffer, named and shaped as in model.state_dict():
+        `sd = model.state_dict(); sd.update(optimizer.ema_state_dict())` loads into this model or the reference's"""
+        self._need_ema("ema_state_dict")
+        gb, src = self.gb, self._ema_src()
+        return {n: src[off:off + p.numel()].view(p.shape).clone() for n, p, off in zip(gb.names, gb.params, gb.offsets)}
+
+    @torch.no_grad()
+    def load_ema_state_dict(self, sd):
+        """the inverse of ema_state_dict(): every tensor of the gradient buffer must be there; other keys (buffers,
+        frozen tensors) are ignored"""
+        self._need_ema("load_ema_state_dict")
+        gb, dst = self.gb, self._ema_src()
+        missing = [n for n in gb.names if n not in sd]
+        if missing:
+            raise KeyError("load_ema_state_dict: %d tensors missing, the first is %s" % (len(missing), missing[0]))
+        for n, p, off in zip(gb.names, gb.params, gb.offsets):
+            if tuple(sd[n].shape) != tuple(p.shape):
+                raise ValueError("load_ema_state_dict: %s has shape %s, the model's is %s"
+                                 % (n, tuple(sd[n].shape), tuple(p.shape)))
+            dst[off:off + p.numel()].copy_(sd[n].reshape(-1))
+
     # ------------------------------------------------------------------ optimizer protocol
     @torch.no_grad()
     def step(self, closure=None, grad_clip=0.0):
@@ -282,6 +439,7 @@ class FlatAdamW(torch.optim.Optimizer):
         gradients themselves are left unscaled).  The norm is that of the WHOLE flat gradient buffer, whichever
         tensors this optimizer covers."""
         assert closure is None
+        ema = self._ema_args() if self._ema_on else None  # (refuses inside swap_ema() before anything is written)
         self.sync_hyperparameters()
         active = self._tags() if self._grouped else self._active_mask()
         if grad_clip and grad_clip > 0:
@@ -292,19 +450,23 @@ class FlatAdamW(torch.optim.Optimizer):
             self.step_t += 1
             self.last_norm = None
         if self._grouped:
-            check(lib().mesm_adamw_step_groups(ptr(self.flat_p), ptr(self.gb.flat), ptr(self.exp_avg),
-                                               ptr(self.exp_avg_sq), ptr(active), self.flat_p.numel(), ptr(partials),
-                                               n_p, float(grad_clip or 0.0), ptr(self._table), len(self._step0),
-                                               ptr(self.step_t), ptr(self.last_norm), stream_ptr()),
-                  "mesm_adamw_step_groups")
+            args = (ptr(self.flat_p), ptr(self.gb.flat), ptr(self.exp_avg), ptr(self.exp_avg_sq), ptr(active),
+                    self.flat_p.numel(), ptr(partials), n_p, float(grad_clip or 0.0), ptr(self._table), len(self._step0),
+                    ptr(self.step_t), ptr(self.last_norm))
+            if ema is not None:
+                check(lib().mesm_adamw_step_groups_ema(*args, *ema, stream_ptr()), "mesm_adamw_step_groups_ema")
+            else:
+                check(lib().mesm_adamw_step_groups(*args, stream_ptr()), "mesm_adamw_step_groups")
             return
         g = self.param_groups[0]
         b1, b2 = g["betas"]
-        check(lib().mesm_adamw_step(ptr(self.flat_p), ptr(self.gb.flat), ptr(self.exp_avg), ptr(self.exp_avg_sq),
-                                    ptr(active), self.flat_p.numel(), ptr(partials), n_p,
-                                    float(grad_clip or 0.0), ptr(self.lr_t), float(b1), float(b2),
-                                    float(g["eps"]), float(g["weight_decay"]), ptr(self.step_t),
-                                    ptr(self.last_norm), stream_ptr()), "mesm_adamw_step")
+        args = (ptr(self.flat_p), ptr(self.gb.flat), ptr(self.exp_avg), ptr(self.exp_avg_sq), ptr(active),
+                self.flat_p.numel(), ptr(partials), n_p, float(grad_clip or 0.0), ptr(self.lr_t), float(b1), float(b2),
+                float(g["eps"]), float(g["weight_decay"]), ptr(self.step_t), ptr(self.last_norm))
+        if ema is not None:
+            check(lib().mesm_adamw_step_ema(*args, *ema, stream_ptr()), "mesm_adamw_step_ema")
+        else:
+            check(lib().mesm_adamw_step(*args, stream_ptr()), "mesm_adamw_step")
 
     # ------------------------------------------------------------------ the tail captured in a micro-stepped graph
     def set_coverage(self, has_grad):
@@ -326,7 +488,7 @@ class FlatAdamW(torch.optim.Optimizer):
     def captured_ptrs(self):
         """addresses a captured tail bakes in (GraphedStep compares them before every replay)"""
         ts = (self.flat_p, self.exp_avg, self.exp_avg_sq, self.step_t, self.lr_t, self._table, self._cap_tags,
-              self._cap_partials, self._cap_norm)
+              self._cap_partials, self._cap_norm, self.ema, self._ema_state, self.last_ema_decay)
         return [t.data_ptr() if t is not None else 0 for t in ts]
 
     @torch.no_grad()
@@ -340,6 +502,7 @@ class FlatAdamW(torch.optim.Optimizer):
         table."""
         if self._cap_tags is None:
             raise RuntimeError("FlatAdamW.step_gated: call set_coverage() first")
+        ema = self._ema_args() if self._ema_on else None
         if not torch.cuda.is_current_stream_capturing():
             self.sync_hyperparameters()
         n_p = ctypes.c_int32(0)
@@ -350,23 +513,31 @@ class FlatAdamW(torch.optim.Optimizer):
         clip = clip if clip > 0 else 0.0
         self.last_norm = self._cap_norm
         if self._grouped:
-            check(lib().mesm_adamw_step_groups_gated(ptr(self.flat_p), ptr(flat), ptr(self.exp_avg), ptr(self.exp_avg_sq),
-                                                     ptr(self._cap_tags), self.flat_p.numel(), ptr(self._cap_partials),
-                                                     n_p.value, clip, ptr(self._table), len(self._step0),
-                                                     ptr(self.step_t), ptr(self._cap_norm), ptr(due), stream_ptr()),
-                  "mesm_adamw_step_groups_gated")
+            args = (ptr(self.flat_p), ptr(flat), ptr(self.exp_avg), ptr(self.exp_avg_sq), ptr(self._cap_tags),
+                    self.flat_p.numel(), ptr(self._cap_partials), n_p.value, clip, ptr(self._table), len(self._step0),
+                    ptr(self.step_t), ptr(self._cap_norm), ptr(due))
+            if ema is not None:
+                check(lib().mesm_adamw_step_groups_ema_gated(*args, *ema, stream_ptr()), "mesm_adamw_step_groups_ema_gated")
+            else:
+                check(lib().mesm_adamw_step_groups_gated(*args, stream_ptr()), "mesm_adamw_step_groups_gated")
             return
         g = self.param_groups[0]
         b1, b2 = g["betas"]
         self._cap_baked = (float(b1), float(b2), float(g["eps"]), float(g["weight_decay"]))
-        check(lib().mesm_adamw_step_gated(ptr(self.flat_p), ptr(flat), ptr(self.exp_avg), ptr(self.exp_avg_sq),
-                                          ptr(self._cap_tags), self.flat_p.numel(), ptr(self._cap_partials), n_p.value,
-                                          clip, ptr(self.lr_t), *self._cap_baked, ptr(self.step_t), ptr(self._cap_norm),
-                                          ptr(due), stream_ptr()), "mesm_adamw_step_gated")
+        args = (ptr(self.flat_p), ptr(flat), ptr(self.exp_avg), ptr(self.exp_avg_sq), ptr(self._cap_tags),
+                self.flat_p.numel(), ptr(self._cap_partials), n_p.value, clip, ptr(self.lr_t), *self._cap_baked,
+                ptr(self.step_t), ptr(self._cap_norm), ptr(due))
+        if ema is not None:
+            check(lib().mesm_adamw_step_ema_gated(*args, *ema, stream_ptr()), "mesm_adamw_step_ema_gated")
+        else:
+            check(lib().mesm_adamw_step_gated(*args, stream_ptr()), "mesm_adamw_step_gated")
 
     def check_captured(self):
         """before a replay of a captured step_gated(): RuntimeError when the default form's by-value hyperparameters
-        were edited since the capture (the replay would go on using the old ones)"""
+        were edited since the capture (the replay would go on using the old ones), or inside swap_ema() (the update
+        would train the average)"""
+        if self._swapped:
+            raise RuntimeError("FlatAdamW: no replay of a captured update inside swap_ema() (the parameters hold the average)")
         if self._cap_baked is not None:
             g = self.param_groups[0]
             now = (float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]))
@@ -400,7 +571,13 @@ class FlatAdamW(torch.optim.Optimizer):
             out = {k: v for k, v in g.items() if k != "params"}
             out["params"] = list(range(i - len(members), i))
             groups.append(out)
-        return {"state": state, "param_groups": groups}
+        sd = {"state": state, "param_groups": groups}
+        if self._ema_on:  # (torch.optim.AdamW.load_state_dict takes a dict with this extra key and drops it)
+            src = self._ema_src()
+            sd["ema"] = {"decay": self._ema_decay, "warmup": bool(self.ema_warmup), "num_updates": step - self._ema_step0,
+                         "params": [src[off:off + p.numel()].view(p.shape).clone()
+                                    for members in self._members() for p, off in members]}
+        return sd
 
     def load_state_dict(self, sd):
         self._ensure()
@@ -437,6 +614,23 @@ class FlatAdamW(torch.optim.Optimizer):
                 if k != "params":
                     g[k] = v
         self._hyper_host = None
+        if not self._ema_on:
+            return  # (an "ema" key is ignored)
+        saved_ema = sd.get("ema")
+        if saved_ema is None:
+            self.reset_ema()
+            return
+        flat_members = [m for ms in members for m in ms]
+        if len(saved_ema["params"]) != len(flat_members):
+            raise ValueError("loaded state dict's EMA has %d tensors, the optimizer covers %d"
+                             % (len(saved_ema["params"]), len(flat_members)))
+        dst = self._ema_src()
+        for t, (p, off) in zip(saved_ema["params"], flat_members):
+            dst[off:off + p.numel()].copy_(t.reshape(-1))
+        self._ema_decay = _check_ema_decay(saved_ema["decay"])
+        self.ema_warmup = bool(saved_ema["warmup"])
+        self._ema_step0 = total - int(saved_ema["num_updates"])
+        self._sync_ema()
 
 
 def param_groups(model, rules=(), no_decay_1d=False, **defaults):
@@ -484,6 +678,7 @@ def param_groups(model, rules=(), no_decay_1d=False, **defaults):
 
 def build_optimizer(opt, model):
     """runner.py:348-352 with the flat AdamW: (optimizer, StepLR scheduler)."""
-    optimizer = FlatAdamW(model, lr=opt.lr, weight_decay=opt.weight_decay)
+    optimizer = FlatAdamW(model, lr=opt.lr, weight_decay=opt.weight_decay, ema_decay=getattr(opt, "ema_decay", None),
+                          ema_warmup=getattr(opt, "ema_warmup", False))
     lr_scheduler = torch.optim.lr_scheduler.StepLR(optimizer, opt.lr_drop, gamma=opt.gamma)
     return optimizer, lr_scheduler
