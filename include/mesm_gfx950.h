@@ -1011,6 +1011,38 @@ int mesm_adamw_step_groups_ema_gated(float* p, const float* g, float* m, float* 
                                      float* norm_out, const int32_t* due, float* ema, const MesmEmaState* es,
                                      float* decay_out, void* stream);
 int mesm_swap_f32(float* a, float* b, int64_t n, void* stream);
+/* Skipping a non-finite update on the device (no counterpart in the reference; the device-side equivalent of torch's
+ * GradScaler found_inf skip).  One launch between mesm_grad_sumsq[_gated] and a *_gated update, which takes `go` as its
+ * due word:
+ *   norm = the total norm of the partials (np of them, 1..1024), the expression of the update entries on the same
+ *   operands, so its bits are theirs.  With due != NULL and *due == 0 the launch writes *go = 0 and nothing else.
+ *   Otherwise gs->attempts += 1, *norm_out = norm (optional), and
+ *     norm finite:      *go = 1, gs->consecutive = 0;
+ *     norm non-finite:  *go = 0, *step -= 1 (undoes the increment of the sum of squares: bias corrections and every step0
+ *                       behave as if the batch had never been seen), gs->skipped += 1, gs->consecutive += 1,
+ *                       gs->last_skipped_attempt = gs->attempts, and for every segment s the number of non-finite
+ *                       elements of g in float4s [seg_start4[s], seg_start4[s + 1]) is ADDED to seg_elems[s].
+ *   seg_start4 (n_seg + 1 ascending float4 indices, device memory) names the tensors of the flat layout; an element no
+ *   segment holds is not counted.  seg_elems (n_seg 64-bit counters) is cumulative: the launch never clears it, the sums
+ *   are integer and so independent of arrival order.  A norm that is non-finite although every element is finite (the
+ *   sum of squares overflowed) skips the update and moves no counter.  *go is written by every launch.  Up to 2048
+ *   segments the table and one counter per segment sit in LDS and a workgroup issues one global atomic per segment it
+ *   met; beyond, the table is searched in global memory and the workgroup's counters are 2048 hashed LDS slots (a run
+ *   goes to seg_elems directly only when another segment of the same workgroup holds its slot).  The finite path reads
+ *   the partials and ends.
+ *   MESM_EINVAL: a null g/seg_start4/partials/step/gs/go/seg_elems, n <= 0, n % 4, n / 4 >= 2^31, n_seg outside
+ *   1..MESM_GUARD_MAX_SEGMENTS, np outside 1..1024.  MESM_EALIGN: g off a 16-byte boundary, seg_elems off an 8-byte one,
+ *   any other pointer off a 4-byte one.  All checked before the launch. */
+#define MESM_GUARD_MAX_SEGMENTS 65536
+typedef struct MesmGuardState { /* 16 bytes, lives in DEVICE memory; this launch (workgroup 0, lane 0) is the only writer */
+  int32_t attempts;             /* due launches: updates applied + updates skipped */
+  int32_t skipped;              /* of those, the ones with a non-finite norm */
+  int32_t consecutive;          /* skipped since the last applied one */
+  int32_t last_skipped_attempt; /* the value of `attempts` at the last skip, 0: none */
+} MesmGuardState;
+int mesm_grad_guard(const float* g, int64_t n, const int32_t* seg_start4, int32_t n_seg, const float* partials,
+                    int32_t np, const int32_t* due, int32_t* step, MesmGuardState* gs, int32_t* go, float* norm_out,
+                    unsigned long long* seg_elems, void* stream);
 
 /* ------------------------------------------------------------------------- */
 /*

@@ -144,6 +144,15 @@ class EmaState(ctypes.Structure):
                 ("reserved", ctypes.c_int32)]
 
 
+class GuardState(ctypes.Structure):
+    """MesmGuardState: what mesm_grad_guard counts, in device memory"""
+    _fields_ = [("attempts", ctypes.c_int32), ("skipped", ctypes.c_int32), ("consecutive", ctypes.c_int32),
+                ("last_skipped_attempt", ctypes.c_int32)]
+
+
+GUARD_MAX_SEGMENTS = 65536
+
+
 # name -> (restype, argtypes); mirrors include/mesm_gfx950.h one to one.
 _i32, _i64, _f32, _u32 = ctypes.c_int32, ctypes.c_int64, ctypes.c_float, ctypes.c_uint32
 PROTOTYPES = {
@@ -273,6 +282,7 @@ PROTOTYPES = {
     "mesm_adamw_step_groups_ema_gated": (ctypes.c_int, [c_ptr] * 5 + [_i64, c_ptr, _i32, _f32, c_ptr, _i32, c_ptr, c_ptr,
                                                         c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
     "mesm_swap_f32": (ctypes.c_int, [c_ptr, c_ptr, _i64, c_ptr]),
+    "mesm_grad_guard": (ctypes.c_int, [c_ptr, _i64, c_ptr, _i32, c_ptr, _i32] + [c_ptr] * 7),
     "mesm_glue_group": (ctypes.c_int, [ctypes.POINTER(GlueArgs), _i32, c_ptr]),
     "mesm_criterion_fwd": (ctypes.c_int, [ctypes.POINTER(CritFwdArgs), c_ptr]),
     "mesm_criterion_bwd": (ctypes.c_int, [ctypes.POINTER(CritBwdArgs), c_ptr]),

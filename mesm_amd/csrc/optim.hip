@@ -239,11 +239,132 @@ __global__ __launch_bounds__(OPT_THREADS) void swap_kernel(float* __restrict__ a
   }
 }
 
+// The non-finite guard between the sum of squares and a gated update (mesm_grad_guard).  Every workgroup sums the partials
+// with total_norm -- the expression of the update kernels on the same operands, so `finite` is the verdict their norm would
+// give -- and workgroup 0, lane 0 alone writes go, gs, step and norm_out; no workgroup reads a word another one writes in
+// this launch, and none waits for another.  Only a due launch over a non-finite norm goes on to walk g: a lane counts the
+// non-finite elements of its float4s in a register for as long as they fall into one segment (found by binary search in
+// the table of float4 starts, which sits in LDS together with one counter per segment when LDS_TABLE), adds the run to the
+// workgroup's counter when the segment changes, and each workgroup adds its non-zero counters to seg_elems once at the
+// end: integer sums, whatever the arrival order.  Without LDS_TABLE (more than GUARD_LDS_SEGS segments) the table is
+// searched in global memory and the workgroup's counters are a hash table in LDS: slot s % GUARD_LDS_SEGS belongs to the
+// first segment that claims it (one compare-and-swap on its tag), and only a run whose slot another segment of the same
+// workgroup holds goes to seg_elems directly.  A lane's run and a workgroup's counter hold at most
+// 4 * n4 / gridDim.x <= 2^25 (grad_guard_blocks, n4 < 2^31): 32 bits.
+constexpr int GUARD_LDS_SEGS = 2048;
+constexpr int GUARD_BLOCKS = 256;  // one workgroup per CU: the finite path reads np floats per workgroup and ends
+
+__device__ __forceinline__ bool nonfinite(float x) { return (__float_as_uint(x) & 0x7f800000u) == 0x7f800000u; }
+
+template <bool LDS_TABLE>
+__global__ __launch_bounds__(OPT_THREADS) void grad_guard_kernel(
+    const float* __restrict__ g, int64_t n4, const int32_t* __restrict__ seg_start4, int n_seg,
+    const float* __restrict__ partials, int np, const int32_t* __restrict__ due, int32_t* __restrict__ step,
+    MesmGuardState* __restrict__ gs, int32_t* __restrict__ go, float* __restrict__ norm_out,
+    unsigned long long* __restrict__ seg_elems) {
+  const bool lane0 = blockIdx.x == 0 && threadIdx.x == 0;
+  if (due && due[0] == 0) {
+    if (lane0) go[0] = 0;  // (written on every launch: a 1 left by the last cycle would let this replay update)
+    return;
+  }
+  __shared__ float sh[OPT_THREADS / 64];
+  __shared__ int32_t tab_s[LDS_TABLE ? GUARD_LDS_SEGS + 1 : 1];
+  __shared__ int32_t tag_s[LDS_TABLE ? 1 : GUARD_LDS_SEGS];  // the segment that owns a hashed counter, -1: none yet
+  __shared__ uint32_t cnt_s[GUARD_LDS_SEGS];
+  const float norm = total_norm(partials, np, sh);
+  const bool bad = nonfinite(norm);
+  if (lane0) {
+    const int32_t attempt = gs->attempts + 1;
+    gs->attempts = attempt;
+    if (bad) {
+      step[0] -= 1;  // the sum of squares counted an update that will not happen
+      gs->skipped += 1;
+      gs->consecutive += 1;
+      gs->last_skipped_attempt = attempt;
+    } else {
+      gs->consecutive = 0;
+    }
+    go[0] = bad ? 0 : 1;
+    if (norm_out) norm_out[0] = norm;
+  }
+  if (!bad) return;
+  const int32_t* tab = seg_start4;
+  if constexpr (LDS_TABLE) {
+    for (int s = threadIdx.x; s <= n_seg; s += OPT_THREADS) tab_s[s] = seg_start4[s];
+    for (int s = threadIdx.x; s < n_seg; s += OPT_THREADS) cnt_s[s] = 0u;
+    __syncthreads();
+    tab = tab_s;
+  } else {
+    for (int s = threadIdx.x; s < GUARD_LDS_SEGS; s += OPT_THREADS) {
+      tag_s[s] = -1;
+      cnt_s[s] = 0u;
+    }
+    __syncthreads();
+  }
+  int cur = -1;            // the segment of the run, -1: none
+  int32_t b0 = 0, b1 = 0;  // its float4 range [b0, b1)
+  uint32_t run = 0;
+  auto flush = [&]() {
+    if (cur >= 0 && run) {
+      if constexpr (LDS_TABLE) {
+        atomicAdd(&cnt_s[cur], run);
+      } else {
+        const int h = cur & (GUARD_LDS_SEGS - 1);
+        const int32_t owner = atomicCAS(&tag_s[h], -1, cur);
+        if (owner == -1 || owner == cur) atomicAdd(&cnt_s[h], run);
+        else atomicAdd(&seg_elems[cur], (unsigned long long)run);
+      }
+    }
+    run = 0;
+  };
+  for (int64_t i = (int64_t)blockIdx.x * OPT_THREADS + threadIdx.x; i < n4; i += (int64_t)gridDim.x * OPT_THREADS) {
+    const float4 v = reinterpret_cast<const float4*>(g)[i];
+    const uint32_t k = (uint32_t)nonfinite(v.x) + (uint32_t)nonfinite(v.y) + (uint32_t)nonfinite(v.z) + (uint32_t)nonfinite(v.w);
+    if (k == 0) continue;
+    const int32_t i4 = (int32_t)i;
+    if (i4 < b0 || i4 >= b1) {
+      flush();
+      int lo = 0, hi = n_seg;  // the last s in [0, n_seg) with tab[s] <= i4 (0 when there is none): always inside the table
+      while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (tab[mid] <= i4) lo = mid; else hi = mid;
+      }
+      cur = lo;
+      b0 = tab[lo];
+      b1 = tab[lo + 1];
+      if (i4 < b0 || i4 >= b1) {  // an element no segment holds is not counted
+        cur = -1;
+        b0 = b1 = 0;
+        continue;
+      }
+    }
+    run += k;
+  }
+  flush();
+  __syncthreads();
+  if constexpr (LDS_TABLE) {
+    for (int s = threadIdx.x; s < n_seg; s += OPT_THREADS) {
+      const uint32_t c = cnt_s[s];
+      if (c) atomicAdd(&seg_elems[s], (unsigned long long)c);
+    }
+  } else {
+    for (int h = threadIdx.x; h < GUARD_LDS_SEGS; h += OPT_THREADS) {
+      const uint32_t c = cnt_s[h];
+      if (c) atomicAdd(&seg_elems[tag_s[h]], (unsigned long long)c);  // (a counter that is not 0 has an owner)
+    }
+  }
+}
+
 inline int opt_blocks(int64_t n4) {
   int64_t b = (n4 + OPT_THREADS - 1) / OPT_THREADS;
   if (b > 1024) b = 1024;
   if (b < 1) b = 1;
   return (int)b;
+}
+
+inline int grad_guard_blocks(int64_t n4) {
+  const int64_t b = (n4 + OPT_THREADS - 1) / OPT_THREADS;
+  return (int)(b < GUARD_BLOCKS ? b : GUARD_BLOCKS);
 }
 
 template <bool GATED>
@@ -396,5 +517,25 @@ extern "C" int mesm_swap_f32(float* a, float* b, int64_t n, void* stream) {
   if ((((uintptr_t)a | (uintptr_t)b) & 15) != 0) return MESM_EALIGN;
   if (a == b) return 0;
   hipLaunchKernelGGL(swap_kernel, dim3(opt_blocks(n / 4)), dim3(OPT_THREADS), 0, (hipStream_t)stream, a, b, n / 4);
+  return mesm_launch_status();
+}
+
+extern "C" int mesm_grad_guard(const float* g, int64_t n, const int32_t* seg_start4, int32_t n_seg, const float* partials,
+                               int32_t np, const int32_t* due, int32_t* step, MesmGuardState* gs, int32_t* go,
+                               float* norm_out, unsigned long long* seg_elems, void* stream) {
+  if (!g || !seg_start4 || !partials || !step || !gs || !go || !seg_elems || n <= 0 || (n & 3)) return MESM_EINVAL;
+  if (n / 4 > INT32_MAX || n_seg < 1 || n_seg > MESM_GUARD_MAX_SEGMENTS || np <= 0 || np > 1024) return MESM_EINVAL;
+  if ((uintptr_t)g & 15) return MESM_EALIGN;
+  if ((((uintptr_t)seg_start4 | (uintptr_t)due | (uintptr_t)step | (uintptr_t)gs | (uintptr_t)go | (uintptr_t)norm_out) & 3) ||
+      ((uintptr_t)seg_elems & 7))
+    return MESM_EALIGN;
+  const int64_t n4 = n / 4;
+  const int nb = grad_guard_blocks(n4);
+  if (n_seg <= GUARD_LDS_SEGS)
+    hipLaunchKernelGGL(grad_guard_kernel<true>, dim3(nb), dim3(OPT_THREADS), 0, (hipStream_t)stream, g, n4, seg_start4, n_seg,
+                       partials, np, due, step, gs, go, norm_out, seg_elems);
+  else
+    hipLaunchKernelGGL(grad_guard_kernel<false>, dim3(nb), dim3(OPT_THREADS), 0, (hipStream_t)stream, g, n4, seg_start4,
+                       n_seg, partials, np, due, step, gs, go, norm_out, seg_elems);
   return mesm_launch_status();
 }

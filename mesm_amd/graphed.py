@@ -308,8 +308,10 @@ class GraphedStep:
             # host edits of the hyperparameters reach the device BEFORE the snapshot: the warm-up passes would upload them
             # after it, and the restore would put the old device words back under a host that believes them current
             opt.sync_hyperparameters()
-            # (with a weight EMA: the average, its decay words and the decay of the last update as well)
-            st["opt"] = [(t, t.clone()) for t in [opt.flat_p, opt.exp_avg, opt.exp_avg_sq, opt.step_t] + opt.ema_tensors()]
+            # (with a weight EMA: the average, its decay words and the decay of the last update as well; with the non-finite
+            # guard: its counters and `go` word, so that the warm-up passes leave no attempt behind)
+            st["opt"] = [(t, t.clone()) for t in [opt.flat_p, opt.exp_avg, opt.exp_avg_sq, opt.step_t] + opt.ema_tensors()
+                         + opt.guard_tensors()]
             st["norm"] = opt._cap_norm.clone() if opt._cap_norm is not None else None
         return st
 

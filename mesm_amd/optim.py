@@ -38,6 +38,15 @@ flat buffer -- train on the raw weights, evaluate and checkpoint the averaged on
     ...
     with optimizer.swap_ema():              # the parameters hold the average inside the block; no address moves
         eval_epoch(model, ...)
+
+Non-finite gradients (`skip_nonfinite=True`): one more launch between the sum of squares and the update (mesm_grad_guard)
+looks at the total norm ON THE DEVICE; when it is inf or NaN the update is skipped as a whole -- parameters, moments, EMA and
+step count keep their bits -- and the tensors that hold the bad elements are counted, with no host synchronisation:
+
+    optimizer = FlatAdamW(model, lr=opt.lr, skip_nonfinite=True)
+    ...
+    if it % 1000 == 0 and optimizer.skipped_updates:        # (reads one device word)
+        print(optimizer.nonfinite_report()["since_last_report"])
 """
 import contextlib
 import ctypes
@@ -82,6 +91,27 @@ def tag_table(gb, group_of, has_grad):
         if on and k >= 0:
             tags[off // 4:(off + p.numel() + 3) // 4] = k + 1
     return tags
+
+
+def segment_table(gb):
+    """The tensors of a GradBuffer as mesm_grad_guard's segment table, on the host: (starts, order).  `starts` (int32,
+    len(gb.params) + 1 entries) holds the first float4 of every tensor in ascending order plus the end of the buffer --
+    gradbuf.py pads every tensor to a multiple of 4 elements and leaves no gap, so segment j is float4s
+    [starts[j], starts[j + 1]) -- and `order[j]` is the index of segment j's tensor in gb.names / gb.params.  Packs permute
+    the offsets, so the table is NOT in parameter order."""
+    order = sorted(range(len(gb.params)), key=lambda i: gb.offsets[i])
+    starts = [gb.offsets[i] // 4 for i in order] + [gb.numel // 4]
+    for j, i in enumerate(order):
+        assert gb.offsets[i] % 4 == 0 and gb.offsets[i] + (gb.params[i].numel() + 3) // 4 * 4 == 4 * starts[j + 1], gb.names[i]
+    return torch.tensor(starts, dtype=torch.int32), order
+
+
+def check_guard_segments(n_seg):
+    """mesm_grad_guard's limit on the number of segments, in words"""
+    if not 1 <= n_seg <= _lib.GUARD_MAX_SEGMENTS:
+        raise _lib.MesmError("skip_nonfinite: the non-finite guard (mesm_grad_guard) names the tensors at fault through a table "
+                             "of 1 to %d segments, and the gradient buffer holds %d tensors"
+                             % (_lib.GUARD_MAX_SEGMENTS, n_seg))
 
 
 def _v_scale(beta2, t):
@@ -140,10 +170,24 @@ class FlatAdamW(torch.optim.Optimizer):
     words, so a captured update follows it without a new capture; `last_ema_decay` is the decay the last update used (a
     device scalar).  The average starts as a copy of the weights and starts over (`reset_ema()`) whenever
     `model.load_state_dict` brings other weights.  `swap_ema()` exchanges weights and average in place for evaluation,
-    `ema_state_dict()` gives the average under the model's key names, and `state_dict()` carries it under "ema"."""
+    `ema_state_dict()` gives the average under the model's key names, and `state_dict()` carries it under "ema".
+
+    `skip_nonfinite=True` (False: nothing below exists, and every launch sequence is the one without it) skips an update
+    whose total gradient norm is inf or NaN, on the device.  step() and step_gated() then always run the sum of squares,
+    mesm_grad_guard behind it, and the `_gated` twin of the update entry behind a device word `go` that the guard writes: a
+    skipped update leaves parameters, moments, EMA, `last_ema_decay` and the step count (so bias corrections, every group's
+    step0 and `num_updates`) as if the batch had never been seen; `last_norm` shows the non-finite norm.  The norm is that
+    of the WHOLE flat gradient buffer, as for clipping: a non-finite element in a tensor this optimizer does not cover
+    skips the update as well.  `skipped_updates` reads one device word; `nonfinite_report()` names the tensors whose
+    gradients held inf / NaN and how many elements each, or says that the sum of squares overflowed over finite elements.
+    `state_dict()` carries {"skipped", "attempts"} under "nonfinite".  As with torch's GradScaler, a host LR scheduler knows
+    nothing of a skip and keeps stepping."""
 
     def __init__(self, model, params=None, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2,
-                 amsgrad=False, maximize=False, ema_decay=None, ema_warmup=False):
+                 amsgrad=False, maximize=False, ema_decay=None, ema_warmup=False, skip_nonfinite=False):
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self._guard_state = self._guard_go = self._guard_counts = self._guard_table = None
+        self._guard_order = self._guard_last = None
         self._ema_on = ema_decay is not None
         self._ema_decay = _check_ema_decay(ema_decay) if self._ema_on else None
         self.ema_warmup = bool(ema_warmup)
@@ -253,6 +297,14 @@ class FlatAdamW(torch.optim.Optimizer):
             self.last_ema_decay = torch.zeros(1, device=dev, dtype=torch.float32)
             self._ema_step0, self._ema_host = 0, None
             self._sync_ema()  # (the device words are valid from here on, whoever reads or snapshots them)
+        if self.skip_nonfinite:
+            table, self._guard_order = segment_table(gb)
+            check_guard_segments(len(self._guard_order))
+            self._guard_table = table.to(dev)
+            self._guard_state = torch.zeros(4, device=dev, dtype=torch.int32)  # MesmGuardState
+            self._guard_go = torch.zeros(1, device=dev, dtype=torch.int32)
+            self._guard_counts = torch.zeros(len(self._guard_order), device=dev, dtype=torch.int64)
+            self._guard_last = None
         if self._grouped:
             nbytes = _lib.ADAM_MAX_GROUPS * ctypes.sizeof(_lib.AdamGroup)
             self._table = torch.zeros(nbytes, device=dev, dtype=torch.uint8)
@@ -432,13 +484,107 @@ class FlatAdamW(torch.optim.Optimizer):
                                  % (n, tuple(sd[n].shape), tuple(p.shape)))
             dst[off:off + p.numel()].copy_(sd[n].reshape(-1))
 
+    # ------------------------------------------------------------------ non-finite guard
+    def guard_tensors(self):
+        """what skip_nonfinite adds to the optimizer's device state ([] when it is off): the MesmGuardState words, the `go`
+        word the guarded update is gated by and the per-tensor element counts (the segment table is constant)"""
+        if self._guard_state is None:
+            return []
+        return [self._guard_state, self._guard_go, self._guard_counts]
+
+    def _need_guard(self, what):
+        if not self.skip_nonfinite:
+            raise RuntimeError("FlatAdamW.%s: the optimizer was built without skip_nonfinite" % what)
+        self._ensure()
+
+    def _guard(self, partials, n_p, due, norm):
+        """mesm_grad_guard behind a sum of squares -> the device word that gates the update"""
+        flat = self.gb.flat
+        check(lib().mesm_grad_guard(ptr(flat), flat.numel(), ptr(self._guard_table), len(self._guard_order), ptr(partials),
+                                    n_p, ptr(due), ptr(self.step_t), ptr(self._guard_state), ptr(self._guard_go), ptr(norm),
+                                    ptr(self._guard_counts), stream_ptr()), "mesm_grad_guard")
+        return self._guard_go
+
+    @property
+    def skipped_updates(self):
+        """updates skipped over a non-finite gradient norm so far (reads one device word: synchronises)"""
+        self._need_guard("skipped_updates")
+        return int(self._guard_state[1].item())
+
+    def nonfinite_report(self):
+        """The guard's counters (synchronises): attempts (updates applied + skipped), skipped, consecutive (skipped since the
+        last applied one), last_skipped_attempt (1-based, 0: none), and under "elements" {tensor name: non-finite gradient
+        elements seen in skipped updates}, cumulative, tensors without any left out.  "since_last_report" holds the
+        difference to the previous call (the host keeps the last copy): "skipped", "elements", and "norm_overflow" -- True
+        when updates were skipped and no count moved, i.e. the sum of squares overflowed over finite elements."""
+        self._need_guard("nonfinite_report")
+        st = [int(x) for x in self._guard_state.tolist()]
+        counts = np.array(self._guard_counts.tolist(), dtype=np.int64)
+        last_skipped, last_counts = self._guard_last or (0, np.zeros_like(counts))
+        self._guard_last = (st[1], counts)
+        names = [self.gb.names[i] for i in self._guard_order]
+        delta = counts - last_counts
+        return {"attempts": st[0], "skipped": st[1], "consecutive": st[2], "last_skipped_attempt": st[3],
+                "elements": {n: int(c) for n, c in zip(names, counts) if c},
+                "since_last_report": {"skipped": st[1] - last_skipped,
+                                      "elements": {n: int(d) for n, d in zip(names, delta) if d},
+                                      "norm_overflow": bool(st[1] > last_skipped and not delta.any())}}
+
+    def _update_guarded(self, tags, partials, n_p, clip, norm, go, ema, baked=None):
+        """the `_gated` twin of the update entry that the form (default / groups) and `ema` select, gated by the guard's word"""
+        name = "mesm_adamw_step"
+        if self._grouped:
+            name += "_groups"
+            hyper = (ptr(self._table), len(self._step0))
+        else:
+            if baked is None:
+                g = self.param_groups[0]
+                baked = (float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]))
+            hyper = (ptr(self.lr_t), *baked)
+        name += "_ema_gated" if ema is not None else "_gated"
+        args = (ptr(self.flat_p), ptr(self.gb.flat), ptr(self.exp_avg), ptr(self.exp_avg_sq), ptr(tags), self.flat_p.numel(),
+                ptr(partials), n_p, clip, *hyper, ptr(self.step_t), ptr(norm), ptr(go), *(ema or ()))
+        check(getattr(lib(), name)(*args, stream_ptr()), name)
+
+    def _step_guarded(self, grad_clip):
+        """step() with skip_nonfinite: sum of squares (always), guard, gated update on the guard's word"""
+        ema = self._ema_args() if self._ema_on else None  # (refuses inside swap_ema() before anything is written)
+        self.sync_hyperparameters()
+        active = self._tags() if self._grouped else self._active_mask()
+        clip = float(grad_clip or 0.0)
+        partials, n_p = _sumsq(self.gb, self.step_t)
+        self.last_norm = torch.empty(1, device=self.flat_p.device, dtype=torch.float32)
+        go = self._guard(partials, n_p, None, self.last_norm)
+        self._update_guarded(active, partials, n_p, clip if clip > 0 else 0.0, self.last_norm, go, ema)
+
+    def _step_gated_guarded(self, due, grad_clip):
+        """step_gated() with skip_nonfinite: gated sum of squares, guard on the same `due`, gated update on the guard's word"""
+        ema = self._ema_args() if self._ema_on else None
+        if not torch.cuda.is_current_stream_capturing():
+            self.sync_hyperparameters()
+        n_p = ctypes.c_int32(0)
+        flat = self.gb.flat
+        check(lib().mesm_grad_sumsq_gated(ptr(flat), flat.numel(), ptr(self._cap_partials), ctypes.byref(n_p),
+                                          ptr(self.step_t), ptr(due), stream_ptr()), "mesm_grad_sumsq_gated")
+        clip = float(grad_clip or 0.0)
+        self.last_norm = self._cap_norm
+        go = self._guard(self._cap_partials, n_p.value, due, self._cap_norm)
+        if not self._grouped:
+            g = self.param_groups[0]
+            self._cap_baked = (float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]))
+        self._update_guarded(self._cap_tags, self._cap_partials, n_p.value, clip if clip > 0 else 0.0, self._cap_norm, go, ema,
+                             self._cap_baked)
+
     # ------------------------------------------------------------------ optimizer protocol
     @torch.no_grad()
     def step(self, closure=None, grad_clip=0.0):
         """grad_clip > 0 fuses nn.utils.clip_grad_norm_(model.parameters(), grad_clip) into the update (the
         gradients themselves are left unscaled).  The norm is that of the WHOLE flat gradient buffer, whichever
-        tensors this optimizer covers."""
+        tensors this optimizer covers.  With skip_nonfinite the sum of squares runs without clipping too, the guard behind
+        it, and the update is the gated entry behind the guard's word (_step_guarded)."""
         assert closure is None
+        if self.skip_nonfinite:
+            return self._step_guarded(grad_clip)
         ema = self._ema_args() if self._ema_on else None  # (refuses inside swap_ema() before anything is written)
         self.sync_hyperparameters()
         active = self._tags() if self._grouped else self._active_mask()
@@ -489,6 +635,8 @@ class FlatAdamW(torch.optim.Optimizer):
         """addresses a captured tail bakes in (GraphedStep compares them before every replay)"""
         ts = (self.flat_p, self.exp_avg, self.exp_avg_sq, self.step_t, self.lr_t, self._table, self._cap_tags,
               self._cap_partials, self._cap_norm, self.ema, self._ema_state, self.last_ema_decay)
+        if self.skip_nonfinite:
+            ts += (*self.guard_tensors(), self._guard_table)
         return [t.data_ptr() if t is not None else 0 for t in ts]
 
     @torch.no_grad()
@@ -499,9 +647,12 @@ class FlatAdamW(torch.optim.Optimizer):
         without clipping too: it is what advances the step count under the gate.  Coverage comes from set_coverage().
         The default form reads lr from the device; betas, eps and weight_decay are launch arguments, fixed at capture
         (`check_captured()` refuses a replay after they were edited); the grouped form reads all of them from its device
-        table."""
+        table.  With skip_nonfinite there are three launches (_step_gated_guarded): the guard sits between the two, looks at
+        `due` itself and gates the update by its own word, which it clears on a replay that is not due."""
         if self._cap_tags is None:
             raise RuntimeError("FlatAdamW.step_gated: call set_coverage() first")
+        if self.skip_nonfinite:
+            return self._step_gated_guarded(due, grad_clip)
         ema = self._ema_args() if self._ema_on else None
         if not torch.cuda.is_current_stream_capturing():
             self.sync_hyperparameters()
@@ -577,6 +728,9 @@ class FlatAdamW(torch.optim.Optimizer):
             sd["ema"] = {"decay": self._ema_decay, "warmup": bool(self.ema_warmup), "num_updates": step - self._ema_step0,
                          "params": [src[off:off + p.numel()].view(p.shape).clone()
                                     for members in self._members() for p, off in members]}
+        if self.skip_nonfinite:  # (an extra key like "ema")
+            st = self._guard_state.tolist()
+            sd["nonfinite"] = {"skipped": int(st[1]), "attempts": int(st[0])}
         return sd
 
     def load_state_dict(self, sd):
@@ -614,6 +768,13 @@ class FlatAdamW(torch.optim.Optimizer):
                 if k != "params":
                     g[k] = v
         self._hyper_host = None
+        if self.skip_nonfinite:  # (without the flag a "nonfinite" key is ignored)
+            # the two totals travel; the per-tensor counts describe the run that made them and start over
+            saved_nf = sd.get("nonfinite") or {"skipped": 0, "attempts": 0}
+            self._guard_state.copy_(torch.tensor([int(saved_nf["attempts"]), int(saved_nf["skipped"]), 0, 0],
+                                                 dtype=torch.int32))
+            self._guard_counts.zero_()
+            self._guard_last = (int(saved_nf["skipped"]), np.zeros(len(self._guard_order), dtype=np.int64))
         if not self._ema_on:
             return  # (an "ema" key is ignored)
         saved_ema = sd.get("ema")
@@ -679,6 +840,7 @@ def param_groups(model, rules=(), no_decay_1d=False, **defaults):
 def build_optimizer(opt, model):
     """runner.py:348-352 with the flat AdamW: (optimizer, StepLR scheduler)."""
     optimizer = FlatAdamW(model, lr=opt.lr, weight_decay=opt.weight_decay, ema_decay=getattr(opt, "ema_decay", None),
-                          ema_warmup=getattr(opt, "ema_warmup", False))
+                          ema_warmup=getattr(opt, "ema_warmup", False),
+                          skip_nonfinite=getattr(opt, "skip_nonfinite", False))
     lr_scheduler = torch.optim.lr_scheduler.StepLR(optimizer, opt.lr_drop, gamma=opt.gamma)
     return optimizer, lr_scheduler
