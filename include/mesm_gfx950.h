@@ -1043,6 +1043,42 @@ typedef struct MesmGuardState { /* 16 bytes, lives in DEVICE memory; this launch
 int mesm_grad_guard(const float* g, int64_t n, const int32_t* seg_start4, int32_t n_seg, const float* partials,
                     int32_t np, const int32_t* due, int32_t* step, MesmGuardState* gs, int32_t* go, float* norm_out,
                     unsigned long long* seg_elems, void* stream);
+/* Per-tensor statistics of the flat gradient buffer g and the flat parameter buffer p in one launch (no counterpart in
+ * the reference: what `[p.grad.norm() for p in model.parameters()]` costs one launch per tensor for).  It sits behind the
+ * sum of squares and the guard and in front of the update: p is the parameter before the update, g what the update sees.
+ * The launch SAMPLES when (due == NULL or *due != 0) and st->every > 0 and *index % st->every == 0; otherwise it writes
+ * nothing at all.  `index` is a count that no launch writes while this one runs: gs->attempts behind mesm_grad_guard
+ * (a skipped attempt takes *step back, which would repeat), *step otherwise.  A sample sets st->samples += 1,
+ * st->last_attempt = *index, and for every segment s of seg_start4 (mesm_grad_guard's table: float4s
+ * [seg_start4[s], seg_start4[s + 1])) and for x = g, p leaves
+ *     the sum over the segment of (double)x * (double)x, accumulated in fp64 (a square is exact there and neither
+ *     overflows nor underflows; the result is within (elements - 1) * 2^-53 relative of the exact sum, in any order), and
+ *     the maximum over the segment of bits(x) & 0x7fffffff as an unsigned integer (exact; inf is 0x7f800000, a NaN ranks
+ *     above it and shows with its payload).
+ * Non-finite elements are reported as they are: inf or NaN in the sum of their segment, no other segment touched.
+ * Result layout.  With W = mesm_tensor_stats_workgroups(n), C = ceil((n / 4) / W) and S = n_seg + W, workgroup b reduces
+ * float4s [b C, (b + 1) C) and stores, for every non-empty segment s that meets them, its part in slot s + b:
+ *     sumsq[s + b], absmax[s + b] for g and sumsq[S + s + b], absmax[S + s + b] for p       (2 S entries each).
+ * Segment s, when it is not empty, meets workgroups seg_start4[s] / C .. (seg_start4[s + 1] - 1) / C; the caller adds
+ * (takes the maximum of) those slots, in ascending b for a result that does not depend on the run.  A sample overwrites
+ * exactly the slots of such pairs and leaves the others (no pair's) alone; no slot is shared, so the stores are plain,
+ * nothing has to be zeroed between samples and one sample cannot leak into the next.  An element no segment holds is
+ * not counted.  g and p are only read.
+ * The host edits st->every alone (0 pauses sampling); workgroup 0, lane 0 is the only writer of the other words.
+ *   MESM_EINVAL: a null g/p/seg_start4/index/st/sumsq/absmax, n <= 0, n % 4, n / 4 >= 2^31, n_seg outside
+ *   1..MESM_GUARD_MAX_SEGMENTS.  MESM_EALIGN: g or p off a 16-byte boundary, sumsq off an 8-byte one, any other pointer off
+ *   a 4-byte one.  All checked before the launch.  mesm_tensor_stats_workgroups is host arithmetic (MESM_EINVAL for an n
+ *   the launch would refuse). */
+typedef struct MesmStatsState { /* 16 bytes, lives in DEVICE memory */
+  int32_t every;        /* sample when *index % every == 0; 0: never.  Written by the host only */
+  int32_t samples;      /* samples taken so far */
+  int32_t last_attempt; /* *index of the last sample, 0: none */
+  int32_t reserved;
+} MesmStatsState;
+int32_t mesm_tensor_stats_workgroups(int64_t n);
+int mesm_tensor_stats(const float* g, const float* p, int64_t n, const int32_t* seg_start4, int32_t n_seg,
+                      const int32_t* due, const int32_t* index, MesmStatsState* st, double* sumsq, uint32_t* absmax,
+                      void* stream);
 
 /* ------------------------------------------------------------------------- */
 /*

@@ -153,6 +153,12 @@ class GuardState(ctypes.Structure):
 GUARD_MAX_SEGMENTS = 65536
 
 
+class StatsState(ctypes.Structure):
+    """MesmStatsState: the sampling interval (the host's word) and what mesm_tensor_stats counts, in device memory"""
+    _fields_ = [("every", ctypes.c_int32), ("samples", ctypes.c_int32), ("last_attempt", ctypes.c_int32),
+                ("reserved", ctypes.c_int32)]
+
+
 # name -> (restype, argtypes); mirrors include/mesm_gfx950.h one to one.
 _i32, _i64, _f32, _u32 = ctypes.c_int32, ctypes.c_int64, ctypes.c_float, ctypes.c_uint32
 PROTOTYPES = {
@@ -283,6 +289,8 @@ PROTOTYPES = {
                                                         c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
     "mesm_swap_f32": (ctypes.c_int, [c_ptr, c_ptr, _i64, c_ptr]),
     "mesm_grad_guard": (ctypes.c_int, [c_ptr, _i64, c_ptr, _i32, c_ptr, _i32] + [c_ptr] * 7),
+    "mesm_tensor_stats_workgroups": (ctypes.c_int32, [_i64]),
+    "mesm_tensor_stats": (ctypes.c_int, [c_ptr, c_ptr, _i64, c_ptr, _i32] + [c_ptr] * 6),
     "mesm_glue_group": (ctypes.c_int, [ctypes.POINTER(GlueArgs), _i32, c_ptr]),
     "mesm_criterion_fwd": (ctypes.c_int, [ctypes.POINTER(CritFwdArgs), c_ptr]),
     "mesm_criterion_bwd": (ctypes.c_int, [ctypes.POINTER(CritBwdArgs), c_ptr]),

@@ -355,6 +355,165 @@ __global__ __launch_bounds__(OPT_THREADS) void grad_guard_kernel(
   }
 }
 
+// Per-tensor statistics of the flat gradient and parameter buffers (mesm_tensor_stats): for every segment of the table and
+// for g and p each, the sum of squares in fp64 -- an element is widened to double before it is squared, so a square is exact
+// and neither overflows nor underflows -- and the largest magnitude as bits (the unsigned maximum of bits & 0x7fffffff: exact,
+// independent of the order, a NaN above inf).  Workgroup b owns the CONTIGUOUS float4s [b * chunk4, (b + 1) * chunk4): the
+// segments that meet that range are consecutive, so it accumulates them in LDS (per lane a run in registers for as long as
+// its float4s fall into one segment, then ds atomics; the wave's last run through one reduction when the whole wave sits in
+// one segment) and leaves each with PLAIN stores in slot s + b of a table of n_seg + gridDim.x slots: going from one
+// (workgroup, segment) pair that meet to the next raises b, s or both, so no two pairs share a slot, and the host, which knows
+// which workgroups meet a segment from the table and chunk4, adds their slots in ascending order.  Nothing is zeroed in
+// global memory, no workgroup reads or writes a word another one writes in this launch, and none waits; the only words
+// with a single writer are st->samples and st->last_attempt (workgroup 0, lane 0).  A workgroup whose range meets more than
+// STATS_LDS_SEGS segments takes them in windows of that many, one after the other; the table is searched in global memory
+// once, for the first segment of the range, and in LDS after that.  An element in front of the first or behind the last
+// segment falls into no window's segment and is not counted.  Every index is clamped to the buffers whatever the table
+// holds.
+constexpr int STATS_LDS_SEGS = 512;     // 512 * (2 * 8 + 2 * 4) + 513 * 4 bytes of LDS: 14 KiB
+constexpr int STATS_MAX_BLOCKS = 1024;  // four workgroups per CU
+constexpr int STATS_MIN_CHUNK4 = 1024;  // float4s per workgroup before there is a second one
+
+__device__ __forceinline__ double wave_sum_f64(double v) {
+  for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+
+__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
+  for (int o = 32; o; o >>= 1) {
+    const uint32_t w = (uint32_t)__shfl_xor((int)v, o);
+    v = w > v ? w : v;
+  }
+  return v;
+}
+
+__device__ __forceinline__ void stats_take(const float4 v, double& a, uint32_t& m) {
+  const double x = (double)v.x, y = (double)v.y, z = (double)v.z, w = (double)v.w;
+  a += x * x;  // (exact products: fp64 holds the square of any float)
+  a += y * y;
+  a += z * z;
+  a += w * w;
+  const uint32_t bx = __float_as_uint(v.x) & 0x7fffffffu, by = __float_as_uint(v.y) & 0x7fffffffu;
+  const uint32_t bz = __float_as_uint(v.z) & 0x7fffffffu, bw = __float_as_uint(v.w) & 0x7fffffffu;
+  const uint32_t mxy = bx > by ? bx : by, mzw = bz > bw ? bz : bw;
+  const uint32_t q = mxy > mzw ? mxy : mzw;
+  m = q > m ? q : m;
+}
+
+__global__ __launch_bounds__(OPT_THREADS) void tensor_stats_kernel(
+    const float* __restrict__ g, const float* __restrict__ p, int32_t n4, int32_t chunk4,
+    const int32_t* __restrict__ seg_start4, int n_seg, const int32_t* __restrict__ due, const int32_t* __restrict__ index,
+    MesmStatsState* st, double* __restrict__ sumsq, uint32_t* __restrict__ absmax) {
+  if (due && due[0] == 0) return;
+  const int32_t every = st->every, idx = index[0];
+  if (every <= 0 || idx % every != 0) return;  // (the same verdict in every workgroup: nobody writes these words here)
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    st->samples += 1;
+    st->last_attempt = idx;
+  }
+  __shared__ int32_t tab_s[STATS_LDS_SEGS + 1];
+  __shared__ double ss_s[2][STATS_LDS_SEGS];
+  __shared__ uint32_t mx_s[2][STATS_LDS_SEGS];
+  const int64_t first = (int64_t)blockIdx.x * chunk4;
+  if (first >= n4) return;
+  int32_t lo = (int32_t)first;
+  const int32_t hi = (int32_t)(first + chunk4 < (int64_t)n4 ? first + chunk4 : (int64_t)n4);
+  // the last segment that starts at or before lo (the one that holds it; 0 when there is none), found by the whole workgroup
+  // in two counting passes over the ascending table, every `stride`-th entry and then the entries of one stride: two global
+  // loads in a row, where a binary search is a chain of up to 16 with every workgroup of the launch waiting on its own
+  const int stride = (n_seg + OPT_THREADS - 1) / OPT_THREADS;
+  const int j1 = (int)threadIdx.x * stride;
+  int s = __syncthreads_count(j1 < n_seg && seg_start4[j1] <= lo);
+  s = s > 0 ? (s - 1) * stride : 0;
+  if (stride > 1) {
+    const int j2 = s + (int)threadIdx.x;
+    const int c = __syncthreads_count((int)threadIdx.x < stride && j2 < n_seg && seg_start4[j2] <= lo);
+    s += c > 0 ? c - 1 : 0;
+  }
+  const int64_t n_slots = (int64_t)n_seg + gridDim.x;
+  while (lo < hi && s < n_seg) {
+    const int cnt = n_seg - s < STATS_LDS_SEGS ? n_seg - s : STATS_LDS_SEGS;
+    for (int j = threadIdx.x; j <= cnt; j += OPT_THREADS) tab_s[j] = seg_start4[s + j];
+    for (int j = threadIdx.x; j < cnt; j += OPT_THREADS) {
+      ss_s[0][j] = ss_s[1][j] = 0.0;
+      mx_s[0][j] = mx_s[1][j] = 0u;
+    }
+    __syncthreads();
+    int32_t whi = tab_s[cnt] < hi ? tab_s[cnt] : hi;  // this window ends with its last segment or with the range
+    if (whi < lo) whi = lo;
+    int cur = -1;            // the segment of the run (window-relative), -1: none
+    int32_t b0 = 0, b1 = 0;  // its float4 range [b0, b1)
+    double ag = 0.0, ap = 0.0;
+    uint32_t mg = 0u, mp = 0u;
+    auto flush = [&]() {
+      if (cur >= 0) {
+        atomicAdd(&ss_s[0][cur], ag);
+        atomicAdd(&ss_s[1][cur], ap);
+        atomicMax(&mx_s[0][cur], mg);
+        atomicMax(&mx_s[1][cur], mp);
+      }
+      ag = ap = 0.0;
+      mg = mp = 0u;
+    };
+    for (int64_t i = (int64_t)lo + threadIdx.x; i < whi; i += OPT_THREADS) {
+      const float4 gv = reinterpret_cast<const float4*>(g)[i];
+      const float4 pv = reinterpret_cast<const float4*>(p)[i];
+      const int32_t i4 = (int32_t)i;
+      if (i4 < b0 || i4 >= b1) {
+        flush();
+        int a = 0;  // the last j in [0, cnt) with tab_s[j] <= i4 (0 when there is none): always inside the window
+        for (int b = cnt; b - a > 1;) {
+          const int mid = (a + b) >> 1;
+          if (tab_s[mid] <= i4) a = mid; else b = mid;
+        }
+        cur = a;
+        b0 = tab_s[a];
+        b1 = tab_s[a + 1];
+        if (i4 < b0 || i4 >= b1) {  // an element no segment holds is not counted
+          cur = -1;
+          b0 = b1 = 0;
+          continue;
+        }
+      }
+      stats_take(gv, ag, mg);
+      stats_take(pv, ap, mp);
+    }
+    // the last run: one reduction and one lane's atomics when the whole wave ends in one segment (the usual case: a
+    // tensor is much longer than a workgroup's range), every lane's own otherwise
+    const int cur0 = __builtin_amdgcn_readfirstlane(cur);
+    if (__all(cur == cur0)) {
+      ag = wave_sum_f64(ag);
+      ap = wave_sum_f64(ap);
+      mg = wave_max_u32(mg);
+      mp = wave_max_u32(mp);
+      if ((threadIdx.x & 63) == 0) flush();
+    } else {
+      flush();
+    }
+    __syncthreads();
+    for (int j = threadIdx.x; j < cnt; j += OPT_THREADS) {
+      const int32_t t0 = tab_s[j], t1 = tab_s[j + 1];
+      if (t0 < t1 && t1 > lo && t0 < whi) {  // the segment meets [lo, whi): slot s + b is this pair's alone
+        const int64_t slot = (int64_t)s + j + blockIdx.x;
+        sumsq[slot] = ss_s[0][j];
+        sumsq[n_slots + slot] = ss_s[1][j];
+        absmax[slot] = mx_s[0][j];
+        absmax[n_slots + slot] = mx_s[1][j];
+      }
+    }
+    __syncthreads();
+    lo = whi;
+    s += cnt;
+  }
+}
+
+inline int tensor_stats_blocks(int64_t n4) {
+  int64_t b = (n4 + STATS_MIN_CHUNK4 - 1) / STATS_MIN_CHUNK4;
+  if (b > STATS_MAX_BLOCKS) b = STATS_MAX_BLOCKS;
+  if (b < 1) b = 1;
+  return (int)b;
+}
+
 inline int opt_blocks(int64_t n4) {
   int64_t b = (n4 + OPT_THREADS - 1) / OPT_THREADS;
   if (b > 1024) b = 1024;
@@ -537,5 +696,27 @@ extern "C" int mesm_grad_guard(const float* g, int64_t n, const int32_t* seg_sta
   else
     hipLaunchKernelGGL(grad_guard_kernel<false>, dim3(nb), dim3(OPT_THREADS), 0, (hipStream_t)stream, g, n4, seg_start4,
                        n_seg, partials, np, due, step, gs, go, norm_out, seg_elems);
+  return mesm_launch_status();
+}
+
+extern "C" int32_t mesm_tensor_stats_workgroups(int64_t n) {
+  if (n <= 0 || (n & 3) || n / 4 > INT32_MAX) return MESM_EINVAL;
+  return tensor_stats_blocks(n / 4);
+}
+
+extern "C" int mesm_tensor_stats(const float* g, const float* p, int64_t n, const int32_t* seg_start4, int32_t n_seg,
+                                 const int32_t* due, const int32_t* index, MesmStatsState* st, double* sumsq,
+                                 uint32_t* absmax, void* stream) {
+  if (!g || !p || !seg_start4 || !index || !st || !sumsq || !absmax || n <= 0 || (n & 3)) return MESM_EINVAL;
+  if (n / 4 > INT32_MAX || n_seg < 1 || n_seg > MESM_GUARD_MAX_SEGMENTS) return MESM_EINVAL;
+  if ((((uintptr_t)g | (uintptr_t)p) & 15) != 0) return MESM_EALIGN;
+  if ((((uintptr_t)seg_start4 | (uintptr_t)due | (uintptr_t)index | (uintptr_t)st | (uintptr_t)absmax) & 3) ||
+      ((uintptr_t)sumsq & 7))
+    return MESM_EALIGN;
+  const int64_t n4 = n / 4;
+  const int nb = tensor_stats_blocks(n4);
+  const int32_t chunk4 = (int32_t)((n4 + nb - 1) / nb);
+  hipLaunchKernelGGL(tensor_stats_kernel, dim3(nb), dim3(OPT_THREADS), 0, (hipStream_t)stream, g, p, (int32_t)n4, chunk4,
+                     seg_start4, n_seg, due, index, st, sumsq, absmax);
   return mesm_launch_status();
 }

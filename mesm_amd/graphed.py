@@ -309,9 +309,10 @@ class GraphedStep:
             # after it, and the restore would put the old device words back under a host that believes them current
             opt.sync_hyperparameters()
             # (with a weight EMA: the average, its decay words and the decay of the last update as well; with the non-finite
-            # guard: its counters and `go` word, so that the warm-up passes leave no attempt behind)
+            # guard: its counters and `go` word, so that the warm-up passes leave no attempt behind; with per-tensor
+            # statistics: the sample count and the result tables, so that a capture takes no sample)
             st["opt"] = [(t, t.clone()) for t in [opt.flat_p, opt.exp_avg, opt.exp_avg_sq, opt.step_t] + opt.ema_tensors()
-                         + opt.guard_tensors()]
+                         + opt.guard_tensors() + opt.tensor_stat_tensors()]
             st["norm"] = opt._cap_norm.clone() if opt._cap_norm is not None else None
         return st
 

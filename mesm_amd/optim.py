@@ -47,6 +47,14 @@ step count keep their bits -- and the tensors that hold the bad elements are cou
     ...
     if it % 1000 == 0 and optimizer.skipped_updates:        # (reads one device word)
         print(optimizer.nonfinite_report()["since_last_report"])
+
+Per-tensor statistics (`tensor_stats=k`): at every k-th update attempt one more launch in front of the update
+(mesm_tensor_stats) reduces the gradient and the parameter buffer per tensor -- sum of squares in fp64, largest magnitude --
+into device memory; nothing is read back until the caller asks:
+
+    optimizer = FlatAdamW(model, lr=opt.lr, tensor_stats=100)
+    ...
+    rep = optimizer.tensor_stats()          # synchronises; {"samples", "attempt", "total_grad_norm", "tensors", "groups"}
 """
 import contextlib
 import ctypes
@@ -106,12 +114,70 @@ def segment_table(gb):
     return torch.tensor(starts, dtype=torch.int32), order
 
 
-def check_guard_segments(n_seg):
-    """mesm_grad_guard's limit on the number of segments, in words"""
+def check_guard_segments(n_seg, what="skip_nonfinite: the non-finite guard (mesm_grad_guard) names the tensors at fault"):
+    """the limit of mesm_grad_guard and mesm_tensor_stats on the number of segments, in words"""
     if not 1 <= n_seg <= _lib.GUARD_MAX_SEGMENTS:
-        raise _lib.MesmError("skip_nonfinite: the non-finite guard (mesm_grad_guard) names the tensors at fault through a table "
-                             "of 1 to %d segments, and the gradient buffer holds %d tensors"
-                             % (_lib.GUARD_MAX_SEGMENTS, n_seg))
+        raise _lib.MesmError("%s through a table of 1 to %d segments, and the gradient buffer holds %d tensors"
+                             % (what, _lib.GUARD_MAX_SEGMENTS, n_seg))
+
+
+def _check_stats_every(every, least):
+    if isinstance(every, bool) or not isinstance(every, (int, np.integer)) or not least <= every < 2 ** 31:
+        raise ValueError("tensor_stats takes None or an int >= 1 (sample every that many update attempts; the attribute "
+                         "tensor_stats_every also takes 0, which pauses sampling), got %r" % (every,))
+    return int(every)
+
+
+def reduce_stat_slots(starts, n4, n_wg, sumsq, absmax):
+    """mesm_tensor_stats' result tables -> per segment, on the host.  `starts`: the n_seg + 1 float4 starts of the segment
+    table; `n4`: float4s in the flat buffers; `n_wg`: the workgroups of the launch (mesm_tensor_stats_workgroups), each of
+    which reduced C = ceil(n4 / n_wg) consecutive float4s and left its part of segment s in slot s + b; `sumsq` (float64)
+    and `absmax` (uint32): the 2 * (n_seg + n_wg) entries each, g first, then p.  Returns (sumsq, absmax) of shape
+    (2, n_seg): the parts of every segment added (maximum taken) in ascending workgroup order, so the same raw tables
+    always give the same bits; an empty segment gives 0."""
+    starts = np.asarray(starts, dtype=np.int64)
+    n_seg = len(starts) - 1
+    n_slots = n_seg + n_wg
+    sumsq = np.asarray(sumsq, dtype=np.float64).reshape(2, n_slots)
+    absmax = np.asarray(absmax, dtype=np.uint32).reshape(2, n_slots)
+    chunk = -(-int(n4) // int(n_wg))
+    full = starts[1:] > starts[:-1]
+    first = np.where(full, starts[:-1] // chunk, 0)
+    count = np.where(full, (starts[1:] - 1) // chunk - first + 1, 0)
+    seg = np.repeat(np.arange(n_seg), count)
+    ramp = np.arange(len(seg)) - np.repeat(np.cumsum(count) - count, count)
+    slot = seg + np.repeat(first, count) + ramp
+    out_s = np.zeros((2, n_seg), dtype=np.float64)
+    out_m = np.zeros((2, n_seg), dtype=np.uint32)
+    for x in range(2):
+        np.add.at(out_s[x], seg, sumsq[x, slot])  # (unbuffered, in the order of `seg`: ascending workgroups)
+        np.maximum.at(out_m[x], seg, absmax[x, slot])
+    return out_s, out_m
+
+
+def tensor_stats_report(names, order, group_of, n_groups, has_grad, samples, attempt, sumsq, absmax):
+    """FlatAdamW.tensor_stats()'s dict from per-segment arrays (reduce_stat_slots), on the host.  `names`, `group_of` (-1: in
+    no group) and `has_grad` are in parameter order (gb.names); `order[j]` is the parameter of segment j (segment_table:
+    packs permute the offsets); `sumsq` / `absmax` have shape (2, n_seg), gradient first.  Norms are square roots of fp64
+    sums; a group's are those of its tensors' sums, and "total_grad_norm" that of all segments -- the whole buffer, like
+    `last_norm`.  absmax comes back as the float whose bits it is (a NaN for a NaN).  Before the first sample the report is
+    empty."""
+    if samples <= 0:
+        return {"samples": 0, "attempt": int(attempt), "total_grad_norm": None, "tensors": {}, "groups": []}
+    sumsq = np.asarray(sumsq, dtype=np.float64)
+    mag = np.ascontiguousarray(np.asarray(absmax, dtype=np.uint32)).view(np.float32)
+    tensors = {}
+    group_sums = np.zeros((n_groups, 2), dtype=np.float64)
+    with np.errstate(invalid="ignore", over="ignore"):
+        for j, i in enumerate(order):
+            tensors[names[i]] = {"grad_norm": float(np.sqrt(sumsq[0, j])), "grad_absmax": float(mag[0, j]),
+                                 "param_norm": float(np.sqrt(sumsq[1, j])), "param_absmax": float(mag[1, j]),
+                                 "has_grad": bool(has_grad[i]) if has_grad is not None else None}
+            if group_of[i] >= 0:
+                group_sums[group_of[i]] += sumsq[:, j]
+        total = float(np.sqrt(np.sum(sumsq[0])))
+        groups = [{"grad_norm": float(np.sqrt(g)), "param_norm": float(np.sqrt(p))} for g, p in group_sums]
+    return {"samples": int(samples), "attempt": int(attempt), "total_grad_norm": total, "tensors": tensors, "groups": groups}
 
 
 def _v_scale(beta2, t):
@@ -181,11 +247,29 @@ class FlatAdamW(torch.optim.Optimizer):
     skips the update as well.  `skipped_updates` reads one device word; `nonfinite_report()` names the tensors whose
     gradients held inf / NaN and how many elements each, or says that the sum of squares overflowed over finite elements.
     `state_dict()` carries {"skipped", "attempts"} under "nonfinite".  As with torch's GradScaler, a host LR scheduler knows
-    nothing of a skip and keeps stepping."""
+    nothing of a skip and keeps stepping.
+
+    `tensor_stats=k` (None: nothing below exists, and every launch sequence is the one without it; otherwise an int >= 1)
+    puts one launch, mesm_tensor_stats, behind the sum of squares and the guard and in front of the update.  At every k-th
+    update ATTEMPT -- the guard's attempt count with skip_nonfinite, so a skipped attempt is sampled like any other and its
+    inf / NaN are reported as they are; the step count without -- it reduces the flat gradient buffer as the update is
+    about to see it (unclipped; the mean of a micro-step cycle) and the parameters as they are before the update, per
+    tensor, to a sum of squares in fp64 and a largest magnitude; at the other attempts, and in a captured tail at the
+    replays that are not due, it writes nothing.  `tensor_stats()` reads the last sample back (it synchronises).
+    `tensor_stats_every` is an attribute: an edit reaches the device with the next `sync_hyperparameters()`, in the same
+    device word, so a captured tail follows it without a new capture; 0 pauses sampling.  The whole buffer is reduced, as
+    for `last_norm`: a tensor without a gradient reports what the buffer holds, and "has_grad" is what the host knew at
+    the last eager step (`p.grad is not None`) or `set_coverage()`.  `state_dict()` does not carry the statistics."""
 
     def __init__(self, model, params=None, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2,
-                 amsgrad=False, maximize=False, ema_decay=None, ema_warmup=False, skip_nonfinite=False):
+                 amsgrad=False, maximize=False, ema_decay=None, ema_warmup=False, skip_nonfinite=False,
+                 tensor_stats=None):
         self.skip_nonfinite = bool(skip_nonfinite)
+        self._stats_on = tensor_stats is not None
+        self._stats_every = _check_stats_every(tensor_stats, 1) if self._stats_on else None
+        self._stats_state = self._stats_sumsq = self._stats_absmax = self._stats_table = None
+        self._stats_order = self._stats_starts = self._stats_host = self._stats_has_grad = None
+        self._stats_wg = 0
         self._guard_state = self._guard_go = self._guard_counts = self._guard_table = None
         self._guard_order = self._guard_last = None
         self._ema_on = ema_decay is not None
@@ -305,6 +389,21 @@ class FlatAdamW(torch.optim.Optimizer):
             self._guard_go = torch.zeros(1, device=dev, dtype=torch.int32)
             self._guard_counts = torch.zeros(len(self._guard_order), device=dev, dtype=torch.int64)
             self._guard_last = None
+        if self._stats_on:
+            table, self._stats_order = segment_table(gb)
+            n_seg = len(self._stats_order)
+            check_guard_segments(n_seg, "tensor_stats: mesm_tensor_stats reduces the tensors")
+            self._stats_starts = table.numpy().astype(np.int64)
+            self._stats_table = self._guard_table if self._guard_table is not None else table.to(dev)
+            self._stats_wg = int(lib().mesm_tensor_stats_workgroups(gb.numel))
+            if self._stats_wg < 1:
+                raise _lib.MesmError("mesm_tensor_stats_workgroups failed with status %d" % self._stats_wg)
+            n_slots = n_seg + self._stats_wg
+            self._stats_state = torch.zeros(4, device=dev, dtype=torch.int32)  # MesmStatsState
+            self._stats_sumsq = torch.zeros(2 * n_slots, device=dev, dtype=torch.float64)
+            self._stats_absmax = torch.zeros(2 * n_slots, device=dev, dtype=torch.int32)  # (bits: read as uint32)
+            self._stats_host = None
+            self._sync_stats()
         if self._grouped:
             nbytes = _lib.ADAM_MAX_GROUPS * ctypes.sizeof(_lib.AdamGroup)
             self._table = torch.zeros(nbytes, device=dev, dtype=torch.uint8)
@@ -358,6 +457,8 @@ class FlatAdamW(torch.optim.Optimizer):
         self._ensure()
         if self._ema_on:
             self._sync_ema()
+        if self._stats_on:
+            self._sync_stats()
         if not self._grouped:
             g = self.param_groups[0]
             if float(g["lr"]) != getattr(self, "_lr_host", None):  # StepLR edits param_groups[0]["lr"]
@@ -530,6 +631,61 @@ class FlatAdamW(torch.optim.Optimizer):
                                       "elements": {n: int(d) for n, d in zip(names, delta) if d},
                                       "norm_overflow": bool(st[1] > last_skipped and not delta.any())}}
 
+    # ------------------------------------------------------------------ per-tensor statistics
+    @property
+    def tensor_stats_every(self):
+        """sample at every that many update attempts (0: paused); None without the switch"""
+        return self._stats_every
+
+    @tensor_stats_every.setter
+    def tensor_stats_every(self, value):
+        if not self._stats_on:
+            raise RuntimeError("FlatAdamW was built without tensor_stats: there is nothing to sample into")
+        self._stats_every = _check_stats_every(value, 0)
+
+    def _sync_stats(self):
+        """the sampling interval into the first word of the device's MesmStatsState when it changed on the host (the other
+        words are the device's own)"""
+        if self._stats_every == self._stats_host:
+            return
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("tensor_stats_every changed: call sync_hyperparameters() before capturing step()")
+        self._stats_state[:1].fill_(self._stats_every)
+        self._stats_host = self._stats_every
+
+    def tensor_stat_tensors(self):
+        """what tensor_stats adds to the optimizer's device state ([] when it is off): the MesmStatsState words and the two
+        result tables (the segment table is constant)"""
+        if self._stats_state is None:
+            return []
+        return [self._stats_state, self._stats_sumsq, self._stats_absmax]
+
+    def _stats(self, due, has_grad):
+        """mesm_tensor_stats behind the sum of squares and the guard, in front of the update"""
+        flat = self.gb.flat
+        index = self._guard_state if self.skip_nonfinite else self.step_t  # (MesmGuardState starts with `attempts`)
+        self._stats_has_grad = has_grad
+        check(lib().mesm_tensor_stats(ptr(flat), ptr(self.flat_p), flat.numel(), ptr(self._stats_table),
+                                      len(self._stats_order), ptr(due), ptr(index), ptr(self._stats_state),
+                                      ptr(self._stats_sumsq), ptr(self._stats_absmax), stream_ptr()), "mesm_tensor_stats")
+
+    def tensor_stats(self):
+        """The last sample (synchronises): {"samples": samples taken so far, "attempt": the attempt the last one saw (the
+        guard's count with skip_nonfinite, the step count without), "total_grad_norm": of the whole gradient buffer,
+        "tensors": {name: {"grad_norm", "grad_absmax", "param_norm", "param_absmax", "has_grad"}} for every tensor of the
+        gradient buffer, "groups": [{"grad_norm", "param_norm"}] per parameter group}.  See tensor_stats_report."""
+        if not self._stats_on:
+            raise RuntimeError("FlatAdamW.tensor_stats: the optimizer was built without tensor_stats")
+        self._ensure()
+        st = [int(x) for x in self._stats_state.tolist()]
+        if st[1] <= 0:
+            return tensor_stats_report(self.gb.names, self._stats_order, self._group_of, len(self._step0), None, 0, st[2],
+                                       None, None)
+        sumsq, absmax = reduce_stat_slots(self._stats_starts, self.gb.numel // 4, self._stats_wg,
+                                          self._stats_sumsq.cpu().numpy(), self._stats_absmax.cpu().numpy().view(np.uint32))
+        return tensor_stats_report(self.gb.names, self._stats_order, self._group_of, len(self._step0), self._stats_has_grad,
+                                   st[1], st[2], sumsq, absmax)
+
     def _update_guarded(self, tags, partials, n_p, clip, norm, go, ema, baked=None):
         """the `_gated` twin of the update entry that the form (default / groups) and `ema` select, gated by the guard's word"""
         name = "mesm_adamw_step"
@@ -555,6 +711,8 @@ class FlatAdamW(torch.optim.Optimizer):
         partials, n_p = _sumsq(self.gb, self.step_t)
         self.last_norm = torch.empty(1, device=self.flat_p.device, dtype=torch.float32)
         go = self._guard(partials, n_p, None, self.last_norm)
+        if self._stats_on:
+            self._stats(None, self._active_key)
         self._update_guarded(active, partials, n_p, clip if clip > 0 else 0.0, self.last_norm, go, ema)
 
     def _step_gated_guarded(self, due, grad_clip):
@@ -569,6 +727,8 @@ class FlatAdamW(torch.optim.Optimizer):
         clip = float(grad_clip or 0.0)
         self.last_norm = self._cap_norm
         go = self._guard(self._cap_partials, n_p.value, due, self._cap_norm)
+        if self._stats_on:
+            self._stats(due, self._stats_has_grad)
         if not self._grouped:
             g = self.param_groups[0]
             self._cap_baked = (float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]))
@@ -595,6 +755,8 @@ class FlatAdamW(torch.optim.Optimizer):
             partials, n_p = None, 0
             self.step_t += 1
             self.last_norm = None
+        if self._stats_on:
+            self._stats(None, self._active_key)
         if self._grouped:
             args = (ptr(self.flat_p), ptr(self.gb.flat), ptr(self.exp_avg), ptr(self.exp_avg_sq), ptr(active),
                     self.flat_p.numel(), ptr(partials), n_p, float(grad_clip or 0.0), ptr(self._table), len(self._step0),
@@ -623,6 +785,8 @@ class FlatAdamW(torch.optim.Optimizer):
         self._ensure()
         gb = self.gb
         host = tag_table(gb, self._group_of if self._grouped else [0] * len(gb.params), tuple(has_grad))
+        if self._stats_on:
+            self._stats_has_grad = tuple(bool(x) for x in has_grad)
         dev = self.flat_p.device
         if self._cap_tags is None:
             self._cap_tags = host.to(dev)
@@ -637,6 +801,8 @@ class FlatAdamW(torch.optim.Optimizer):
               self._cap_partials, self._cap_norm, self.ema, self._ema_state, self.last_ema_decay)
         if self.skip_nonfinite:
             ts += (*self.guard_tensors(), self._guard_table)
+        if self._stats_on:
+            ts += (*self.tensor_stat_tensors(), self._stats_table)
         return [t.data_ptr() if t is not None else 0 for t in ts]
 
     @torch.no_grad()
@@ -663,6 +829,8 @@ class FlatAdamW(torch.optim.Optimizer):
         clip = float(grad_clip or 0.0)
         clip = clip if clip > 0 else 0.0
         self.last_norm = self._cap_norm
+        if self._stats_on:
+            self._stats(due, self._stats_has_grad)
         if self._grouped:
             args = (ptr(self.flat_p), ptr(flat), ptr(self.exp_avg), ptr(self.exp_avg_sq), ptr(self._cap_tags),
                     self.flat_p.numel(), ptr(self._cap_partials), n_p.value, clip, ptr(self._table), len(self._step0),
@@ -841,6 +1009,7 @@ def build_optimizer(opt, model):
     """runner.py:348-352 with the flat AdamW: (optimizer, StepLR scheduler)."""
     optimizer = FlatAdamW(model, lr=opt.lr, weight_decay=opt.weight_decay, ema_decay=getattr(opt, "ema_decay", None),
                           ema_warmup=getattr(opt, "ema_warmup", False),
-                          skip_nonfinite=getattr(opt, "skip_nonfinite", False))
+                          skip_nonfinite=getattr(opt, "skip_nonfinite", False),
+                          tensor_stats=getattr(opt, "tensor_stats", None))
     lr_scheduler = torch.optim.lr_scheduler.StepLR(optimizer, opt.lr_drop, gamma=opt.gamma)
     return optimizer, lr_scheduler
