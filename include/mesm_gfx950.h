@@ -899,6 +899,13 @@ int mesm_skinny_linear_bwd(const float* dz, const float* x, const float* w, floa
  *                      tokens of x (N, Lx, D) (fp16 or fp32), pads zeroed by mask (N, Lm) uint8, sentence =
  *                      masked mean of the un-normalised words, both L2-normalised (eps 1e-5) if normalize.
  * mesm_embed_rows      out[r, :] = table[ids[r], :]   GloveTextEncoder.forward (text_encoder.py:446-454)
+ * mesm_text_cache_store  the text cache's fill (mesm_amd/textcache.py): cache[slots[m], l, :] = hid[rows[m], l, :]
+ *                      for m < M, l < Lw; hid (n_src, Lx, D) fp16 with Lx >= Lw, cache (capacity, Lw, D) fp16,
+ *                      rows / slots int32 device arrays, clamped to [0, n_src) / [0, capacity) whatever they hold.
+ *                      16-byte accesses when D % 8 == 0 and both bases are 16-byte aligned.  M <= 65535.
+ * mesm_text_pool_slots mesm_text_pool (fp16 input) with pair n reading row slots[n] (clamped) of the cache
+ *                      (capacity, Lw, D) instead of row n of a dense tensor: the same kernel body, the same bits as
+ *                      mesm_text_pool on the gathered rows.
  */
 int mesm_clip_embed(const int64_t* ids, const float* tok, const float* pos, void* x, int64_t rows, int32_t L,
                     int32_t D, int32_t vocab, void* stream);
@@ -911,6 +918,11 @@ int mesm_text_pool(const void* x, int32_t x_is_f16, const uint8_t* mask, int32_t
                    int32_t Lw, int32_t D, int32_t normalize, float* words, float* sent, void* stream);
 int mesm_embed_rows(const int64_t* ids, const float* table, float* out, int64_t rows, int32_t D, int32_t vocab,
                     void* stream);
+int mesm_text_cache_store(const void* hid, int32_t n_src, int32_t Lx, const int32_t* rows, const int32_t* slots,
+                          int32_t M, int32_t Lw, int32_t D, void* cache, int32_t capacity, void* stream);
+int mesm_text_pool_slots(const void* cache, int32_t capacity, const int32_t* slots, const uint8_t* mask, int32_t N,
+                         int32_t Lm, int32_t Lw, int32_t D, int32_t normalize, float* words, float* sent,
+                         void* stream);
 
 /* ------------------------------------------------------------------------- */
 /*

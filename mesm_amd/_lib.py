@@ -254,6 +254,8 @@ PROTOTYPES = {
                                      _i32, _i32, _i32, _i32, c_ptr]),
     "mesm_text_pool": (ctypes.c_int, [c_ptr, _i32, c_ptr, _i32, _i32, _i32, _i32, _i32, _i32, c_ptr, c_ptr, c_ptr]),
     "mesm_embed_rows": (ctypes.c_int, [c_ptr, c_ptr, c_ptr, _i64, _i32, _i32, c_ptr]),
+    "mesm_text_cache_store": (ctypes.c_int, [c_ptr, _i32, _i32, c_ptr, c_ptr, _i32, _i32, _i32, c_ptr, _i32, c_ptr]),
+    "mesm_text_pool_slots": (ctypes.c_int, [c_ptr, _i32, c_ptr, c_ptr, _i32, _i32, _i32, _i32, _i32, c_ptr, c_ptr, c_ptr]),
     "mesm_set_loss_fwd_nv": (ctypes.c_int, [c_ptr] * 5 + [_i32, _i32, _i32, _f32, _f32, _f32, _f32, c_ptr, c_ptr, c_ptr, c_ptr]),
     "mesm_set_loss_bwd_nv": (ctypes.c_int, [c_ptr] * 6 + [_i32, _i32, _f32, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
     "mesm_saliency_loss_fwd_nv": (ctypes.c_int, [c_ptr] * 6 + [_i32, _i32, _i32, _f32, _f32, c_ptr, c_ptr, c_ptr]),

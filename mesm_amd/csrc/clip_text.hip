@@ -162,8 +162,11 @@ __global__ __launch_bounds__(256) void gemm_f16_kernel(const AT* __restrict__ A,
 // MESM.CLIP_encode_text / GloVe_encode_text tail (model.py:118-134, 138-143): first Lw tokens, pads zeroed,
 // sentence = sum / count of the UN-normalised words, then both L2-normalised (eps 1e-5) when `normalize`.
 // One workgroup per pair; x is (N, Lx, D) fp16 or fp32 with Lx >= Lw; mask is (N, Lm) with Lm >= Lw.
-template <typename XT>
+// SLOTS (mesm_text_pool_slots): pair n reads row slots[n] of x (the text cache, `capacity` rows) instead of row n --
+// the one difference; every expression below is shared, so the two forms give the same bits for the same rows.
+template <typename XT, bool SLOTS>
 __global__ __launch_bounds__(256) void text_pool_kernel(const XT* __restrict__ x, const uint8_t* __restrict__ mask,
+                                                        const int32_t* __restrict__ slots, int capacity,
                                                         int Lx, int Lm, int Lw, int D, int normalize,
                                                         float* __restrict__ words, float* __restrict__ sent) {
   extern __shared__ float sm[];  // D sentence accumulators + Lw row norms + 8 scratch
@@ -171,7 +174,9 @@ __global__ __launch_bounds__(256) void text_pool_kernel(const XT* __restrict__ x
   float* rn = sm + D;
   float* scratch = rn + Lw;
   const int n = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const XT* xb = x + (int64_t)n * Lx * D;
+  int64_t src = n;
+  if constexpr (SLOTS) src = min(max(slots[n], 0), capacity - 1);  // (clamped whatever the array holds)
+  const XT* xb = x + src * Lx * D;
   const uint8_t* mb = mask + (int64_t)n * Lm;
   float* wb = words + (int64_t)n * Lw * D;
   for (int l = wave; l < Lw; l += 4) {  // row norms
@@ -204,6 +209,24 @@ __global__ __launch_bounds__(256) void text_pool_kernel(const XT* __restrict__ x
   __syncthreads();
   const float nrm = fmaxf(sqrtf(scratch[0] + scratch[1] + scratch[2] + scratch[3]), 1e-5f);
   for (int c = tid; c < D; c += 256) sent[(int64_t)n * D + c] = normalize ? sacc[c] / nrm : sacc[c];
+}
+
+// cache[slots[m], l, :] = hid[rows[m], l, :] for l < Lw: one wave per token row, 16-byte accesses when D % 8 == 0 and
+// both bases are 16-byte aligned (vec), halfs one by one otherwise.  rows / slots are clamped to the two buffers.
+__global__ __launch_bounds__(64) void text_cache_store_kernel(const h16* __restrict__ hid, int n_src, int Lx,
+                                                              const int32_t* __restrict__ rows,
+                                                              const int32_t* __restrict__ slots, int Lw, int D,
+                                                              h16* __restrict__ cache, int capacity, int vec) {
+  const int l = blockIdx.x, m = blockIdx.y, lane = threadIdx.x;
+  const int64_t r = min(max(rows[m], 0), n_src - 1), s = min(max(slots[m], 0), capacity - 1);
+  const h16* src = hid + (r * Lx + l) * D;
+  h16* dst = cache + (s * Lw + l) * D;
+  if (vec) {
+    for (int c = lane * 8; c < D; c += 64 * 8)
+      *reinterpret_cast<h16x8*>(dst + c) = *reinterpret_cast<const h16x8*>(src + c);
+  } else {
+    for (int c = lane; c < D; c += 64) dst[c] = src[c];
+  }
 }
 
 // rows of an fp32 table by int64 index (GloveTextEncoder.forward, text_encoder.py:446-454)
@@ -260,11 +283,34 @@ extern "C" int mesm_text_pool(const void* x, int32_t x_is_f16, const uint8_t* ma
   if (!x || !mask || !words || !sent || N <= 0 || Lw <= 0 || Lw > Lx || Lw > Lm || D <= 0) return MESM_EINVAL;
   const size_t shm = (size_t)(D + Lw + 8) * sizeof(float);
   if (x_is_f16)
-    hipLaunchKernelGGL(text_pool_kernel<h16>, dim3(N), dim3(256), shm, (hipStream_t)stream, (const h16*)x, mask, Lx, Lm,
-                       Lw, D, normalize, words, sent);
+    hipLaunchKernelGGL((text_pool_kernel<h16, false>), dim3(N), dim3(256), shm, (hipStream_t)stream, (const h16*)x, mask,
+                       (const int32_t*)nullptr, 0, Lx, Lm, Lw, D, normalize, words, sent);
   else
-    hipLaunchKernelGGL(text_pool_kernel<float>, dim3(N), dim3(256), shm, (hipStream_t)stream, (const float*)x, mask, Lx,
-                       Lm, Lw, D, normalize, words, sent);
+    hipLaunchKernelGGL((text_pool_kernel<float, false>), dim3(N), dim3(256), shm, (hipStream_t)stream, (const float*)x,
+                       mask, (const int32_t*)nullptr, 0, Lx, Lm, Lw, D, normalize, words, sent);
+  return mesm_launch_status();
+}
+
+extern "C" int mesm_text_cache_store(const void* hid, int32_t n_src, int32_t Lx, const int32_t* rows,
+                                     const int32_t* slots, int32_t M, int32_t Lw, int32_t D, void* cache,
+                                     int32_t capacity, void* stream) {
+  if (!hid || !rows || !slots || !cache || n_src <= 0 || M <= 0 || Lw <= 0 || Lw > Lx || D <= 0 || capacity <= 0)
+    return MESM_EINVAL;
+  if (M > 65535) return MESM_EINVAL;  // (grid.y; a batch's misses)
+  const int vec = (D % 8 == 0 && ((uintptr_t)hid % 16) == 0 && ((uintptr_t)cache % 16) == 0) ? 1 : 0;
+  hipLaunchKernelGGL(text_cache_store_kernel, dim3(Lw, M), dim3(64), 0, (hipStream_t)stream, (const h16*)hid, n_src, Lx,
+                     rows, slots, Lw, D, (h16*)cache, capacity, vec);
+  return mesm_launch_status();
+}
+
+extern "C" int mesm_text_pool_slots(const void* cache, int32_t capacity, const int32_t* slots, const uint8_t* mask,
+                                    int32_t N, int32_t Lm, int32_t Lw, int32_t D, int32_t normalize, float* words,
+                                    float* sent, void* stream) {
+  if (!cache || !slots || !mask || !words || !sent || capacity <= 0 || N <= 0 || Lw <= 0 || Lw > Lm || D <= 0)
+    return MESM_EINVAL;
+  const size_t shm = (size_t)(D + Lw + 8) * sizeof(float);
+  hipLaunchKernelGGL((text_pool_kernel<h16, true>), dim3(N), dim3(256), shm, (hipStream_t)stream, (const h16*)cache, mask,
+                     slots, capacity, Lw, Lm, Lw, D, normalize, words, sent);
   return mesm_launch_status();
 }
 

@@ -154,6 +154,9 @@ class GraphedStep:
         self.model, self.crit = model, criterion
         self.dataset_name = dataset_name
         self.spec = HostSpec.from_model(model, criterion, dataset_name)
+        # the model's text cache (model.text_cache) is part of what the step is captured for: with it the graph holds
+        # mesm_text_pool_slots over the static slot array p.text_slots and no tower; None = captured without
+        self._tc = model._active_text_cache()
         dev = batch["video_feat"].device
         self.dev = dev
         self.batch = dict(batch)  # static inputs: big tensors as given, everything small re-homed in the arena
@@ -176,6 +179,7 @@ class GraphedStep:
             if isinstance(batch.get(k), list):
                 host[k] = [{kk: vv.detach().cpu() for kk, vv in d.items()} for d in batch[k]]
         arr, self._pmeta, self._tmeta, self._wm_cpu = self._host_arrays(host, None, None)
+        text_miss = self._text_lookup(arr)
         self._arr = arr  # host mirror of the arena
         self._draws = (arr["p.neg_index"], arr.get("p.masked_words"))
         self.arena = Arena(arr, dev, first=self.DRAWN)  # the per-step draws sit together at the front
@@ -200,6 +204,9 @@ class GraphedStep:
             self.batch["_target_plan"] = self.tplan
         if self._n_real is not None:
             self.batch["_n_valid"] = v["p.n_valid"]
+        # the capture batch's misses, in front of the warm-up passes (which read the slots like a replay does and count
+        # nothing in the cache's stats)
+        self._text_encode(text_miss)
         gb = model.gradbuf()
         gb.ensure(dev)
         saved_state = None
@@ -394,8 +401,73 @@ class GraphedStep:
     def _host_arrays(self, host, neg_index, masked_words, targets=True):
         """hostplan.HostSpec.host_arrays with this step's groups / capacities: {name: numpy array} of everything small
         the captured step reads, the two metas and the word mask"""
-        return self.spec.host_arrays(host, self._groups, self.caps, self._n_real, neg_index, masked_words, self.BIG,
-                                     targets=targets and self._targets, is_training=self.TRAIN)
+        arr, pmeta, tmeta, wm = self.spec.host_arrays(host, self._groups, self.caps, self._n_real, neg_index, masked_words,
+                                                      self.BIG, targets=targets and self._targets, is_training=self.TRAIN)
+        return self._with_text_slots(arr), pmeta, tmeta, wm
+
+    # ------------------------------------------------------------------ text cache (model.text_cache, textcache.py)
+    def _with_text_slots(self, arr):
+        """`arr` with the plan entry p.text_slots (int32 per pair, zeros until _text_lookup) in front of the criterion's
+        arrays, which stay together at the end of the arena; `arr` itself without a text cache"""
+        if self._tc is None:
+            return arr
+        import numpy as np
+        if "b.words_id" not in arr or arr["b.words_id"].ndim != 2:
+            raise ValueError("%s: the text cache needs the batch's token ids (N, context_length) on the host"
+                             % type(self).__name__)
+        out = {}
+        for k, v in arr.items():
+            if k.startswith("t."):
+                out.setdefault("p.text_slots", np.zeros(arr["p.vpad"].shape[0], dtype=np.int32))
+            out[k] = v
+        out.setdefault("p.text_slots", np.zeros(arr["p.vpad"].shape[0], dtype=np.int32))
+        return out
+
+    def _text_lookup(self, arr):
+        """the slots of the batch's queries into arr["p.text_slots"] (padding pairs are copies of pair 0: its key, its
+        slot) -> the misses, to be encoded by _text_encode once the batch's ids are on the device.  ValueError (more
+        distinct queries than slots) before anything changes; call it after every other check."""
+        if self._tc is None:
+            return None
+        import numpy as np
+        if self._text_pending:
+            self._tc.clear()  # (a load that failed between its lookup and its fill: the table names unwritten slots)
+        ids, P = arr["b.words_id"], arr["p.text_slots"].shape[0]
+        if ids.shape[0] < P:
+            ids = np.concatenate([ids, np.repeat(ids[:1], P - ids.shape[0], axis=0)])
+        slots, rows, dst = self._tc.lookup(ids, self.model.text_encoder.weights_generation)
+        arr["p.text_slots"] = slots
+        self._text_pending = bool(rows)
+        return rows, dst
+
+    _text_pending = False
+
+    def _text_encode(self, miss):
+        """the tower on the loaded batch's missing queries, eagerly on the current stream -- the one the replay runs on,
+        so a rewritten slot stays behind every earlier reader"""
+        if self._tc is None:
+            return
+        try:
+            self.model.text_cache_encode(self._tc, self.batch["words_id"], miss[0], miss[1])  # (empties the table if it fails)
+        finally:
+            self._text_pending = False
+            self._tc_version = self._tc.version
+
+    def _check_text_cache(self):
+        """before a replay: the switch is what the step was captured for (RuntimeError otherwise: load_batch says it with
+        a ValueError, which sends a cache to another graph); and when the cache's table changed since this step's batch
+        was loaded -- another step's batch, an invalidation -- the loaded batch is looked up (and encoded) again"""
+        tc = self._tc
+        if tc is None and self.model._text_cache_req is None:
+            return
+        if self.model._active_text_cache() is not tc:
+            raise RuntimeError("%s: the model's text cache was switched %s after capture; capture again"
+                               % (type(self).__name__, "off or replaced" if tc is not None else "on"))
+        if tc is not None and (tc.version != self._tc_version
+                               or tc._source_gen != self.model.text_encoder.weights_generation):
+            miss = self._text_lookup(self._arr)
+            self.arena.upload(self._arr, only=["p.text_slots"])
+            self._text_encode(miss)
 
     def _param_ptrs(self):
         gb = self.model.gradbuf()
@@ -483,6 +555,7 @@ class GraphedStep:
             self._pending_targets = host
         self._check_fits(self._groups, self._n_real, pmeta)  # (groups and pair count: checked by load_batch)
         self.arena.check(arr)
+        text_miss = self._text_lookup(arr)
         # nothing above modified anything; from here on only copies
         self._arr = arr
         self._draws = (arr["p.neg_index"], arr.get("p.masked_words"))
@@ -506,6 +579,7 @@ class GraphedStep:
                     cur[:v.shape[0]].copy_(v, non_blocking=True)
                 else:
                     self._stage_big(k, cur, v)
+        self._text_encode(text_miss)
         self._turn ^= 1
         self._wm_cpu = wm
 
@@ -513,6 +587,9 @@ class GraphedStep:
 
     def _check_fits(self, groups, n_real, pmeta=None):
         """ValueError unless a batch of these group sizes, this pair-count mode and (given) this plan meta fits the graph"""
+        if self.model._active_text_cache() is not self._tc:
+            raise ValueError("%s: captured %s the model's current text cache" % (type(self).__name__,
+                                                                               "without" if self._tc is None else "with another than"))
         if groups != self._groups and (self.caps.get("M") is None or sum(groups) != sum(self._groups)):
             # exact-extent graphs (caps=None) are tied to their grouping; with capacities any grouping of the
             # same number of pairs fits as long as its largest group does (checked by the plan)
@@ -550,7 +627,7 @@ class GraphedStep:
         self._check_fits(groups, prep["n_real"], prep["pmeta"])
         if {k: prep["caps"].get(k) for k in self.caps} != self.caps:
             raise ValueError("GraphedStep.load_prepared: prepared with other capacities %r (graph: %r)" % (prep["caps"], self.caps))
-        arr = {k: (v.numpy() if torch.is_tensor(v) else v) for k, v in prep["arr"].items()}
+        arr = self._with_text_slots({k: (v.numpy() if torch.is_tensor(v) else v) for k, v in prep["arr"].items()})
         self.arena.check(arr)
         big = prep["big"]
         for k, v in big.items():
@@ -561,6 +638,7 @@ class GraphedStep:
             # load_batch: without it the stale rows of the previous batch would take part in the step)
             if cur.shape[1:] != v.shape[1:] or v.shape[0] > cur.shape[0] or (v.shape[0] < cur.shape[0] and self._n_real is None):
                 raise ValueError("GraphedStep.load_prepared: %s changed shape %s -> %s" % (k, tuple(cur.shape), tuple(v.shape)))
+        text_miss = self._text_lookup(arr)  # (the table lives in this process: workers know no model)
         # nothing above modified anything; from here on: draws, copies
         self._groups, self._n_real = groups, prep["n_real"]
         self._wm_cpu = prep["wm"]
@@ -577,6 +655,7 @@ class GraphedStep:
         self.tplan.sizes, self.tplan.sumT = prep["tmeta"]["sizes"], prep["tmeta"]["sumT"]
         for k, v in big.items():
             self._stage_big(k, self.batch[k], v)
+        self._text_encode(text_miss)
         self._turn ^= 1
 
     _copy_stream = None
@@ -655,6 +734,7 @@ class GraphedStep:
                 "GraphedStep: a parameter or the gradient buffer moved after capture (model.to(), a new "
                 "optimizer flattening the parameters, ...): the graph still points at the old storage. "
                 "Create the optimizer before the GraphedStep, or capture again.")
+        self._check_text_cache()
         if redraw:
             self.redraw()
         if self._cycle is not None:
@@ -717,6 +797,7 @@ class SplitGraphedStep(GraphedStep):
 
     def forward_replay(self):
         self._check_addresses()
+        self._check_text_cache()
         self.g_fwd.replay()
         return self.out
 
@@ -812,6 +893,7 @@ class EvalGraphedStep(GraphedStep):
     def replay(self):
         """replay the captured call on the loaded batch and draws; -> a fresh copy of its pack (caller-owned memory)"""
         self._check_addresses()
+        self._check_text_cache()
         self.graph.replay()
         return self.pack.clone()
 

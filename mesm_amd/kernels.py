@@ -1479,6 +1479,38 @@ def text_pool(x, mask, Lw, normalize=True):
     return words, sent
 
 
+def text_cache_store(hid, rows, slots, cache, Lw):
+    """cache[slots[m], :, :] = hid[rows[m], :Lw, :]: hid (n, Lx, D) fp16, cache (capacity, Lw, D) fp16, rows / slots
+    (M,) int32 on the device (clamped to the buffers by the kernel)."""
+    require_gpu(hid, rows, slots, cache)
+    assert hid.dtype == cache.dtype == torch.float16 and hid.is_contiguous() and cache.is_contiguous()
+    assert rows.dtype == slots.dtype == torch.int32 and rows.is_contiguous() and slots.is_contiguous()
+    n, Lx, D = hid.shape
+    M = rows.numel()
+    assert slots.numel() == M and cache.dim() == 3 and tuple(cache.shape[1:]) == (Lw, D) and Lw <= Lx
+    if M == 0:
+        return
+    check(lib().mesm_text_cache_store(ptr(hid), n, Lx, ptr(rows), ptr(slots), M, Lw, D, ptr(cache), cache.shape[0],
+                                      stream_ptr()), "mesm_text_cache_store")
+
+
+def text_pool_slots(cache, slots, mask, normalize=True):
+    """text_pool with pair n reading cache[slots[n]]: cache (capacity, Lw, D) fp16, slots (N,) int32, mask (N, Lm >= Lw)
+    bool -> words (N, Lw, D) f32, sentence (N, D) f32; the bits of text_pool(cache[slots], mask, Lw, normalize)."""
+    require_gpu(cache, slots, mask)
+    assert cache.dtype == torch.float16 and cache.is_contiguous() and cache.dim() == 3
+    assert slots.dtype == torch.int32 and slots.is_contiguous() and slots.dim() == 1
+    capacity, Lw, D = cache.shape
+    N = slots.numel()
+    m = mask.contiguous()
+    assert m.dtype in (torch.bool, torch.uint8) and m.shape[0] == N and m.shape[1] >= Lw
+    words = torch.empty(N, Lw, D, device=cache.device, dtype=torch.float32)
+    sent = torch.empty(N, D, device=cache.device, dtype=torch.float32)
+    check(lib().mesm_text_pool_slots(ptr(cache), capacity, ptr(slots), ptr(m), N, m.shape[1], Lw, D,
+                                     1 if normalize else 0, ptr(words), ptr(sent), stream_ptr()), "mesm_text_pool_slots")
+    return words, sent
+
+
 def embed_rows(ids, table):
     require_gpu(ids, table)
     assert ids.dtype == torch.int64 and table.dtype == torch.float32 and table.is_contiguous()

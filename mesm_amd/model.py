@@ -141,6 +141,8 @@ class MESM(nn.Module):
         self._step = 0
         self._flat_checked = -1
         self._auto = None
+        self._text_cache = None       # textcache.TextCache while the switch is on
+        self._text_cache_req = "env"  # "env": MESM_TEXT_CACHE decides (read per call); else the capacity asked for / None
 
     # ------------------------------------------------------------------ infrastructure
     def gradbuf(self):
@@ -256,6 +258,101 @@ class MESM(nn.Module):
         Lw = min(self.max_words_l, hid.shape[1])
         words, sent = kn.text_pool(hid, words_mask, Lw, self.normalize_txt)
         return words, sent, words_id[:, :Lw], words_mask[:, :Lw]
+
+    # ------------------------------------------------------------------ text cache (textcache.py)
+    def text_cache(self, capacity):
+        """Keep the frozen CLIP tower's output rows of up to `capacity` queries on the device and run the tower on the
+        queries of a batch that are not there yet (textcache.TextCache); None switches it off.  Off by default;
+        MESM_TEXT_CACHE=<capacity> switches it on for a loop that is not to be edited (an explicit call wins).  The text
+        stage then is: host lookup of the token-id rows -> tower on the misses -> mesm_text_pool_slots, bit for bit the
+        uncached result.  ValueError with a GloVe encoder or none: those text stages have no tower to skip."""
+        if capacity is None:
+            self._text_cache_req, self._text_cache = None, None
+            return None
+        self._refuse_text_cache("text_cache(%r)" % (capacity,))
+        if int(capacity) < 1:
+            raise ValueError("text_cache: capacity must be at least 1, got %r" % (capacity,))
+        self._text_cache_req = int(capacity)
+        self._text_cache = None  # (a new buffer: graphs captured over the old one are not served any more)
+        return self._active_text_cache()
+
+    def _refuse_text_cache(self, what):
+        if not isinstance(self.text_encoder, CLIPTextEncoder):
+            kind = "a GloVe text encoder" if isinstance(self.text_encoder, GloveTextEncoder) else "no text encoder"
+            raise ValueError("%s: the text cache keeps outputs of the frozen CLIP text tower; this model has %s (its text "
+                             "stage is %s)" % (what, kind, "a table lookup" if self.text_encoder is not None else
+                                               "the pre-extracted word features"))
+
+    def _active_text_cache(self):
+        """the TextCache in force for the next call, or None (switch off)"""
+        req = self._text_cache_req
+        if req == "env":
+            env = os.environ.get("MESM_TEXT_CACHE", "")
+            if not env:
+                return None
+            self._refuse_text_cache("MESM_TEXT_CACHE=%s" % env)
+            try:
+                req = int(env)
+            except ValueError:
+                raise ValueError("MESM_TEXT_CACHE=%r: a capacity (number of queries)" % env)
+            if req < 1:
+                raise ValueError("MESM_TEXT_CACHE=%r: capacity must be at least 1" % env)
+        elif req is None:
+            return None
+        te = self.text_encoder
+        dev = te.positional_embedding.device
+        tc = self._text_cache
+        if tc is None or tc.capacity != req or tc.device != dev:
+            from .textcache import TextCache
+            tc = self._text_cache = TextCache(req, min(self.max_words_l, te.context_length), te.transformer.width, dev)
+        return tc
+
+    def text_cache_stats(self):
+        """the counters of the text cache (textcache.TextCache.stats), None while it is off"""
+        tc = self._active_text_cache()
+        if tc is None:
+            return None
+        if tc._source_gen is not None:
+            tc.sync(self.text_encoder.weights_generation)  # (weights loaded since the last lookup: the table is void)
+        return tc.stats()
+
+    def load_state_dict(self, *a, **kw):
+        if isinstance(self.text_encoder, CLIPTextEncoder):
+            self.text_encoder.bump_weights_generation()  # (the module-tree load does not go through the tower's own method)
+        return super().load_state_dict(*a, **kw)
+
+    def text_cache_fill(self, tc, ids_host, words_id):
+        """lookup of the batch's token-id rows (host copy `ids_host`) and the tower on the rows that miss: ONE call over
+        the sub-batch, gathered on the device from `words_id`, stored on the current stream -> slots int32[N] (numpy)"""
+        slots, miss_rows, miss_slots = tc.lookup(ids_host, self.text_encoder.weights_generation)
+        self.text_cache_encode(tc, words_id, miss_rows, miss_slots)
+        return slots
+
+    def text_cache_encode(self, tc, words_id, miss_rows, miss_slots):
+        """second half of text_cache_fill: rows `miss_rows` of the device ids through the tower into `miss_slots`"""
+        if not miss_rows:
+            return
+        try:
+            with torch.no_grad():
+                sub = words_id.index_select(0, torch.as_tensor(miss_rows, dtype=torch.int64).to(words_id.device))
+                hid = self.text_encoder(sub, want_pooler=False)["last_hidden_state"]
+                tc.store(hid, miss_slots)
+        except BaseException:
+            tc.clear()  # (the table names slots that were never written)
+            raise
+
+    def cached_encode_text(self, tc, words_id, words_mask, plan=None, host=None):
+        """CLIP_encode_text through the text cache: the slot of every pair from the plan of a captured step
+        (`plan.text_slots`, filled when the batch was loaded) or from a lookup here, then the pooling over the slots"""
+        slots = getattr(plan, "text_slots", None)
+        if slots is None:
+            ids = host.get("words_id") if isinstance(host, dict) else None
+            if not (torch.is_tensor(ids) and not ids.is_cuda and tuple(ids.shape) == tuple(words_id.shape)
+                    and ids.dtype == torch.int64):
+                ids = words_id.cpu()  # (a small fetch, next to the ones make_plan does)
+            slots = torch.from_numpy(self.text_cache_fill(tc, ids, words_id)).to(words_id.device)
+        words, sent = kn.text_pool_slots(tc.data, slots, words_mask, self.normalize_txt)
+        return words, sent, words_id[:, :tc.Lw], words_mask[:, :tc.Lw]
 
     def GloVe_encode_text(self, words_id, words_mask):
         """model.py:136-143."""
@@ -456,7 +553,11 @@ class MESM(nn.Module):
         N, Lv = video_mask.shape
 
         with _scope("text"):
-            if isinstance(self.text_encoder, CLIPTextEncoder):
+            tc = self._active_text_cache() if (self._text_cache_req is not None) else None
+            if tc is not None:
+                words, sent, words_id, words_mask = self.cached_encode_text(tc, words_id, words_mask, kwargs.get("plan"),
+                                                                            kwargs.get("_host"))
+            elif isinstance(self.text_encoder, CLIPTextEncoder):
                 words, sent, words_id, words_mask = self.CLIP_encode_text(words_id, words_mask)
             elif isinstance(self.text_encoder, GloveTextEncoder):
                 words, sent = self.GloVe_encode_text(words_id, words_mask)

@@ -73,6 +73,8 @@ def build_model(args, vocab=None):
     model.to(args.device)
     if torch.device(args.device).type == "cuda":
         model.flat_params()  # final parameter addresses before any optimizer / HIP-graph capture
+    if getattr(args, "text_cache", None) is not None:
+        model.text_cache(args.text_cache)  # (ValueError without a CLIP tower: refused, not ignored)
     return model
 
 

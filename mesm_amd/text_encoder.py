@@ -122,14 +122,34 @@ class CLIPTextEncoder(nn.Module):
     def dtype(self):
         return torch.float16
 
+    # what a cache of this tower's outputs (textcache.TextCache) keys its validity on: a count of the events after which
+    # the weights may be other ones -- load_state_dict, _apply (.to / .half / .float), convert_weights
+    @property
+    def weights_generation(self):
+        return self.__dict__.get("_weights_gen", 0)
+
+    def bump_weights_generation(self):
+        self.__dict__["_weights_gen"] = self.__dict__.get("_weights_gen", 0) + 1
+
+    def _apply(self, fn, *a, **kw):
+        self.bump_weights_generation()
+        return super()._apply(fn, *a, **kw)
+
+    def load_state_dict(self, *a, **kw):
+        self.bump_weights_generation()  # (before the load: one that fails half-way has changed weights too)
+        return super().load_state_dict(*a, **kw)
+
     @torch.no_grad()
-    def forward(self, text):
-        """text (N, context_length) int64 token ids -> {"last_hidden_state": (N, L, W) fp16}."""
+    def forward(self, text, want_pooler=True):
+        """text (N, context_length) int64 token ids -> {"last_hidden_state": (N, L, W) fp16, "pooler_output"}
+        (want_pooler=False: the hidden states alone, for a caller that reads nothing else -- the text cache's fill)."""
         x = kn.clip_embed(text, self.token_embedding.weight, self.positional_embedding)
         for blk in self.transformer.resblocks:
             x = blk(x)
         N, L, d = x.shape
         x = kn.layernorm_f16(x.view(N * L, d), self.ln_final.weight, self.ln_final.bias).view(N, L, d)
+        if not want_pooler:
+            return dict(last_hidden_state=x)
         # text_encoder.py:352-354: the features of the end-of-text token (the largest id) through text_projection,
         # fp16 like the rest of the tower (MESM itself only reads last_hidden_state)
         eos = x[torch.arange(N, device=x.device), text.argmax(dim=-1)]
@@ -151,6 +171,7 @@ def convert_weights(model):
             m.in_proj_bias.data = m.in_proj_bias.data.half()
         if isinstance(m, CLIPTextEncoder):
             m.text_projection.data = m.text_projection.data.half()
+            m.bump_weights_generation()
 
 
 def clip_text_encoder_from_state_dict(state_dict):
