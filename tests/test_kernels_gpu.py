@@ -8,6 +8,8 @@ import math
 import pytest
 import torch
 
+from loss_ref import saliency as saliency_reference  # (the fp64 restatement of criterion.py:139-221)
+
 pytestmark = pytest.mark.gpu
 
 TOL = 1e-4
@@ -593,36 +595,6 @@ def test_nll_smooth(R, C):
     (ref * w.double()).sum().backward()
     dl = kn.nll_smooth_bwd(logit, label, row_lse, w)
     assert rel_err(dl, ld.grad) < TOL
-
-
-def saliency_reference(s_pos, s_neg, label, vmask, pos_idx, neg_idx, rank_coef, margin):
-    """fp64 restatement of criterion.py:139-221."""
-    vm = vmask.double()
-    N = s_pos.shape[0]
-    loss_neg = (-torch.log(1.0 - torch.sigmoid(s_neg)) * vm).sum(1).mean()
-    sc = torch.cat([s_pos, s_neg], 1)
-    lab = torch.cat([label, torch.zeros_like(label)], 1)
-    vm2 = vm.repeat(1, 2)
-    sc = vm2 * sc + (1.0 - vm2) * -1e3
-    total = 0.0
-    for r in range(1, 12):
-        pos = lab >= r
-        if pos.sum() == 0:
-            continue
-        bd = pos.sum(1) > 0
-        cur = sc / 0.5
-        lg = cur - cur.max(1, keepdim=True)[0]
-        lp = lg - torch.log(torch.exp(lg).sum(1, keepdim=True) + 1e-6)
-        mlp = (pos * lp * vm2).sum(1) / (pos.sum(1) + 1e-6)
-        total = total + (-mlp * bd).mean()
-    total = total / rank_coef + loss_neg
-    if pos_idx is not None:
-        P = pos_idx.shape[1]
-        bi = torch.arange(N, device=s_pos.device)
-        ps = torch.stack([s_pos[bi, pos_idx[:, c]] for c in range(P)], 1)
-        ns = torch.stack([s_pos[bi, neg_idx[:, c]] for c in range(P)], 1)
-        total = total + torch.clamp(margin + ns - ps, min=0).sum() / (N * P) * 2
-    return total
 
 
 @pytest.mark.parametrize("N,L,qvh", [(32, 75, True), (5, 40, False), (3, 600, False)])
